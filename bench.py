@@ -5,7 +5,7 @@ RunSimulation(months{12}) per GPU on BASELINE.json configs[1] (9-miner 2025 netw
 followed by the single exchange step of the path: an RCCL all-reduce of the per-miner integer sums.
 Weak scaling: per-GPU work is fixed; each step and rank takes a fresh, disjoint run range (fresh seeds).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--runs 32768]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--runs 32768] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL over xGMI)
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks itself (one child
@@ -14,8 +14,17 @@ non-zero if any rank fails: the reference's own driver fans out over every hardw
 (main.cpp:198-209).
 
 Rank 0 prints ONE JSON line (driver contract) with a live VALU roofline (HIP events around every launch
-on the launch stream) and, at N=1, the CPU baseline: the oracle (explicit-chain C port of the reference
-loop, oracle/msim_oracle.c) timed on a bounded sample on the host's cores.
+on the launch stream). A plain run does only that: set up, warm up, time the K steps, print the line.
+
+--full adds the measurements that take runs of their own: `serial_single_job` (the same steps on one stream)
+and, at N=1, the CPU baseline: the oracle (explicit-chain C port of the reference loop, oracle/msim_oracle.c)
+timed on a bounded sample on the host's cores (--no-cpu-baseline leaves it out of a --full run).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step's launch handed its caller, as
+DIR/<name>.npy (float64): `sums` [M, 6], the per-miner msim_sums of that step's runs (all-reduced over the
+ranks), `sums_words` [M, 6, 2], the same 64-bit integers as exact (high, low) 32-bit words, and `status` [2].
+Run ranges and seeds depend only on the arguments, so two builds run with the same arguments can be compared
+array for array.
 """
 from __future__ import annotations
 
@@ -317,6 +326,21 @@ class _StubSim:
         status.zero_()
 
 
+def dump_outputs(out_dir: str, lane: dict) -> None:
+    """--dump-outputs: the buffers the last timed step's launch filled for its caller (this lane's, which no later
+    step has overwritten), as float64 .npy files. `sums` rounds a value above 2^53 to the nearest double;
+    `sums_words` holds every 64-bit value exactly as (signed high, unsigned low) 32-bit words."""
+    import numpy as np
+
+    sums = lane["sums"].cpu().numpy()  # int64 [M, 6]; the timed region ended with a device synchronize
+    status = lane["status"].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sums.npy"), sums.astype(np.float64))
+    np.save(os.path.join(out_dir, "sums_words.npy"),
+            np.stack([sums >> 32, sums & 0xFFFFFFFF], axis=-1).astype(np.float64))
+    np.save(os.path.join(out_dir, "status.npy"), status.astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -329,10 +353,16 @@ def main() -> None:
     ap.add_argument("--streams", type=int, default=0,
                     help="HIP streams the steps alternate over (1: serial; 0 = 2: an honest step's latency-bound "
                          "tail kernels, and a selfish launch's last engine waves, overlap the next step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: serial_single_job and, at --gpus 1, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (sums, sums_words, status) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-runs", type=int, default=0, help="0 = auto (~15 s of CPU work)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)  # tests: CPU stand-in, gloo
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -446,6 +476,8 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     tm = timing_read()
     timing_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lanes[(args.warmup + args.steps - 1) % ns])
     assert tm["launches"] == args.steps, tm
     kern_ms = tm["launch_ms"] / args.steps  # all kernels of one msim_launch (K1+K2+K3+finalize), per launch
     k1_ms = tm["draws_ms"] / args.steps     # K1 / W1 per launch (span of each launch's draw kernel)
@@ -480,7 +512,7 @@ def main() -> None:
     # The single-job rate beside the headline: the same steps on ONE stream, each launch waiting for the previous
     # one (nothing overlaps), timed separately after the headline region with the same barrier + synchronize.
     serial = None
-    if ns > 1:
+    if args.full and ns > 1:
         # the same job as a caller with one launch in flight runs it: a config planned for one launch
         # (msim_config_set_concurrent_launches(1), the library's default), its own workspace, one stream
         sim1 = sim if args.stub else Simulation(miners, total_weight=PRESET_WEIGHTS.get(args.config, 100))
@@ -633,7 +665,7 @@ def main() -> None:
             line["rccl"] = rccl
         if args.stub:
             line["data"] = "STUB (--stub: CPU stand-in for the launch, tests of the rank/JSON plumbing only)"
-        if world == 1 and not args.no_cpu_baseline and not args.stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.stub:
             threads, visible, how = host_threads()
             line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_sample_runs, threads, visible)
             line["cpu_baseline"]["cores_note"] = how

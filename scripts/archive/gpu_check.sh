@@ -11,7 +11,7 @@ if [ -z "$NOTEST" ]; then
 fi
 for spec in ${BENCHES:-"c2 1" "c2 0" "c3 0" "c5 0"}; do
   set -- $spec
-  timeout -k 10 300 python -u bench.py --config $1 --streams $2 --no-cpu-baseline > $O/bench_$1_s$2.json 2> $O/bench_$1_s$2.err || { tail -30 $O/bench_$1_s$2.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --config $1 --streams $2 --no-cpu-baseline > $O/bench_$1_s$2.json 2> $O/bench_$1_s$2.err || { tail -30 $O/bench_$1_s$2.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_$1_s$2.json'));r=d['roofline'];print('$1 streams=$2',d['value'],d['ms_per_step'],'kernel',r['kernel_ms'],'k1',r['k1_ms'],'frac',r['frac'])"
 done
 for s in $SLOTS; do

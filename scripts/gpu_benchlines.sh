@@ -8,9 +8,9 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/${TAG:-r05/lines}; mkdir -p $O
 [ -n "$INSTALL" ] && cp $INSTALL/rocprof_*.md profiles/r05/final/
-timeout -k 10 400 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -30 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -30 $O/bench_default.err; exit 1; }
 for c in ${CFGS-c3 c5}; do
-  timeout -k 10 300 python -u bench.py --config $c --no-cpu-baseline > $O/bench_line_$c.json 2> $O/bench_line_$c.err || { tail -30 $O/bench_line_$c.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --config $c --no-cpu-baseline > $O/bench_line_$c.json 2> $O/bench_line_$c.err || { tail -30 $O/bench_line_$c.err; exit 1; }
 done
 for c in ${SERIAL-c2 c3 c5}; do
   timeout -k 10 300 python -u bench.py --config $c --streams 1 --no-cpu-baseline > $O/bench_line_${c}_s1.json 2> $O/bench_line_${c}_s1.err || { tail -30 $O/bench_line_${c}_s1.err; exit 1; }

@@ -8,7 +8,7 @@ O=gpurun_out/${TAG:-r05/e1}; mkdir -p $O
 timeout -k 10 600 python -u -m pytest ${PYTEST_FILES:-tests/test_gpu_selfish.py tests/test_gpu_parity.py tests/test_selkat.py} -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
 tail -1 $O/pytest.log
 for st in 1 2; do
-  timeout -k 10 300 python3 bench.py --config c3 --streams $st --no-cpu-baseline > $O/bench_c3_s$st.json 2> $O/bench_c3_s$st.err || { tail -5 $O/bench_c3_s$st.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --config c3 --streams $st --no-cpu-baseline > $O/bench_c3_s$st.json 2> $O/bench_c3_s$st.err || { tail -5 $O/bench_c3_s$st.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_c3_s$st.json'));print('c3 streams $st',d['value'],d['ms_per_step'])"
 done
 timeout -k 10 300 python3 scripts/bench_sweep.py --runs-per-point 8192 > $O/sweep.json 2> $O/sweep.err || { tail -5 $O/sweep.err; exit 1; }

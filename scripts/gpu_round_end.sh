@@ -10,6 +10,6 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout
 rc=$?; echo "pytest rc=$rc" >> "$OUT/status.txt"; [ $rc -eq 0 ] || stop pytest $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 rc=$?; echo "smoke rc=$rc" >> "$OUT/status.txt"; [ $rc -eq 0 ] || stop smoke $rc
-timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench rc=$rc" >> "$OUT/status.txt"; [ $rc -eq 0 ] || stop bench $rc
 echo done >> "$OUT/status.txt"

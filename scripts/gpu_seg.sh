@@ -11,7 +11,7 @@ if [ -z "$NOTEST" ]; then
 fi
 for s in ${STREAMS:-1 0}; do
   B=""; [ $s = 1 ] && B="--streams 1"
-  MSIM_SELSEG=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_c3_s$s -o prof -- python3 bench.py --config c3 $B --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline > $O/bench_c3_s$s.json 2> $O/prof_c3_s$s.err || { tail -20 $O/prof_c3_s$s.err; exit 1; }
+  MSIM_SELSEG=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_c3_s$s -o prof -- python3 bench.py --full --config c3 $B --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline > $O/bench_c3_s$s.json 2> $O/prof_c3_s$s.err || { tail -20 $O/prof_c3_s$s.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_c3_s$s.json'));print('seg c3 s$s',d['value'],d['ms_per_step'])"
   python3 scripts/rocprof_summary.py $O/prof_c3_s$s > $O/rocprof_c3_s$s.md
   head -8 $O/rocprof_c3_s$s.md

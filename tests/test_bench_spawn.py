@@ -78,3 +78,26 @@ def test_spawn_failing_rank_ends_job():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert "rank 1 exited" in r.stderr, r.stderr[-2000:]
     assert time.monotonic() - t0 < 120
+
+
+def test_plain_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """A plain run prints the headline fields only; --full adds serial_single_job. --dump-outputs writes the
+    last timed step's arrays, identical for identical arguments whatever else the run measures."""
+    import numpy as np
+
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", a)
+    assert "serial_single_job" not in d and "cpu_baseline" not in d
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3
+    f = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", b)
+    assert f["serial_single_job"]["steps"] == 3
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b)) == ["status.npy", "sums.npy", "sums_words.npy"]
+    for name in os.listdir(a):
+        x, y = np.load(os.path.join(a, name)), np.load(os.path.join(b, name))
+        assert x.dtype == np.float64 and x.shape == y.shape and np.array_equal(x, y), name
+    s, w = np.load(os.path.join(a, "sums.npy")), np.load(os.path.join(a, "sums_words.npy"))
+    assert s.shape == (9, 6) and w.shape == (9, 6, 2)
+    assert np.array_equal(w[..., 0] * 2.0**32 + w[..., 1], s)  # the stub's values are small: both forms exact
+    assert np.array_equal(s, np.arange(54, dtype=np.float64).reshape(9, 6) + 32768)
