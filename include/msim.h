@@ -96,7 +96,16 @@ int msim_config_create(const msim_miner *miners, uint32_t n, int64_t duration_ms
 int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t duration_ms, uint64_t total_weight,
                                 msim_config **out);
 /* 1 when the config runs on the large-network pipeline (set MSIM_FORCE_WIDE=1 in the environment before
- * msim_config_create to route small honest networks there too, e.g. for cross-path parity checks). */
+ * msim_config_create to route small honest networks there too, e.g. for cross-path parity checks).
+ * A second test switch, MSIM_MAX_SLICE_RUNS=<n> (n > 0), read at every sizing and launch call: a slice of the
+ * honest pipeline, the large-network pipeline and the entity engine (single networks, the opt-in
+ * segment-parallel form and sweeps) holds at most n runs, rounded up to a multiple of 256, so a few hundred
+ * runs exercise the slice loops that otherwise begin past 16 GiB of workspace or 2^22 runs per point.
+ * msim_workspace_bytes, msim_launch, msim_run, msim_pipeline_info (slice_runs) and the sweep and multi-GPU
+ * entry points all follow it; the general engine has no slices. Unset, nothing changes.
+ * A third, MSIM_PIPE_FORCE_RETRY (set to anything), read at every launch of the honest pipeline: its combine
+ * kernel flags every run, so the retry kernel computes them all (what MSIM_SEL_FORCE_RETRY does on the entity
+ * engine); at most 65 536 runs per launch then, the retry list's size. */
 int msim_config_is_wide(const msim_config *cfg);
 /* How many launches of this config the caller keeps in flight at once (default 1; e.g. 2 when steps
  * alternate over two HIP streams). The event-skipping pipeline plans its draw kernel's grid for it: three

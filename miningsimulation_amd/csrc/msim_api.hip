@@ -170,6 +170,19 @@ SweepLayout sweep_layout(uint32_t m, uint32_t n_points, uint64_t rpp)
 constexpr double PIPE_MAX_RHO = 0.08;           // above this the per-lane kernel is cheaper
 constexpr double PIPE_SLICE_BUDGET = 16.0 * (1ull << 30);  // pipeline workspace per slice (bytes)
 
+// Test switch (MSIM_MAX_SLICE_RUNS=<n>, n > 0): a slice of the honest pipeline, the large-network pipeline and
+// the entity engine (single network and sweep) holds at most n runs, rounded up to a multiple of 256, so that a
+// few hundred runs take the slice loops a launch otherwise enters only past 16 GiB of workspace or 2^22 runs
+// per point. 0: no cap. pipe_layout, wide_layout and sel_ws_layout apply it, and every size and launch goes
+// through those three.
+uint32_t max_slice_runs()
+{
+    const char *e = getenv("MSIM_MAX_SLICE_RUNS");
+    const long long v = e ? atoll(e) : 0;
+    if (v <= 0) return 0;
+    return v >= (1ll << 22) ? 1u << 22 : (uint32_t)((v + 255) / 256 * 256);
+}
+
 // K1 wave slots of the current device (CUs x resident K1 waves per CU); 8192 if it cannot be queried.
 uint32_t draw_slots()
 {
@@ -191,7 +204,9 @@ msim::PipeLayout pipe_layout(const msim_config *c, uint64_t n_runs)
     const uint32_t jobs = c->jobs ? c->jobs : 1u;
     uint32_t slots = jobs == 1u ? draw_slots() * 3u : draw_slots() * 2u / jobs;
     if (slots < 1u) slots = 1u;
-    return msim::pipe_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, PIPE_SLICE_BUDGET, slots);
+    const msim::PipeLayout L = msim::pipe_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, PIPE_SLICE_BUDGET, slots);
+    const uint32_t cap = max_slice_runs();  // the layout of a slice of exactly `cap` runs, not a smaller budget's
+    return cap && L.nr > cap ? msim::pipe_layout_nr(c->rho, c->n, c->p.duration_ms, cap, slots) : L;
 }
 
 // Pipeline tables for this config on the current device: pick table, log table, jump matrices for
@@ -274,7 +289,7 @@ constexpr double WIDE_SLICE_BUDGET = 16.0 * (1ull << 30);
 
 msim::WideLayout wide_layout(const msim_config *c, uint64_t n_runs)
 {
-    return msim::wide_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, WIDE_SLICE_BUDGET);
+    return msim::wide_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, WIDE_SLICE_BUDGET, max_slice_runs());
 }
 
 // Device tables of a wide config (msim_wide_launch.h WideArgs) on the current device, uploaded once.
@@ -372,7 +387,9 @@ SelWs sel_ws_layout(uint32_t m, uint32_t np, uint64_t rpp, int64_t duration_ms, 
 {
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     SelWs w;
-    // one slice of every run (up to 2^22 runs per point: cold slots ~1.4 GiB)
+    // one slice of every run (up to 2^22 runs per point: cold slots ~1.4 GiB; fewer under MSIM_MAX_SLICE_RUNS,
+    // which thereby caps the segment-parallel form too: its records are laid out for this nr, sel_cfg_layout)
+    if (const uint32_t cap = max_slice_runs()) max_nr = cap < max_nr ? cap : max_nr;
     const uint64_t want = (rpp + 255) / 256 * 256;
     w.nr = (uint32_t)(want < max_nr ? want : max_nr);
     w.wpp = (uint32_t)((rpp + msim::TPB - 1) / msim::TPB);

@@ -9,6 +9,7 @@
 // Roofline: VALU issue (no MFMA: nothing is a dense contraction; no HBM stream: each lane reads its
 // parameters once and writes ~6*M words per 256 runs). See DESIGN.md §4.
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 
 #include "msim_kernels.h"
 #include "msim_reduce.h"
@@ -319,6 +320,12 @@ static hipError_t launch_pipeline(const LaunchArgs &a, uint64_t *parts)
     da.grec = (GroupRec *)(ws + L.grec_off);
     da.list = (EpEntry *)(ws + L.list_off);
     da.list_count = (uint32_t *)(ws + L.count_off);
+    // Test switch (MSIM_PIPE_FORCE_RETRY, the pipeline's MSIM_SEL_FORCE_RETRY): K3 is given a band that begins past
+    // the last segment, so combine_run flags every run at its first check (the run ends before the band) and the
+    // retry kernel computes them all. The pipeline's own retries need an 8-sigma event, so nothing else sends the
+    // run indices of a second slice through the retry list. K1 and K2 keep the true band.
+    PipeArgs pk3 = pa;
+    if (getenv("MSIM_PIPE_FORCE_RETRY") != nullptr) pk3.band_lo = pa.nseg;
     uint32_t ep_grid = (L.lcap + K2_TPB - 1) / K2_TPB;
     if (ep_grid > 8192u * (TPB / K2_TPB)) ep_grid = 8192u * (TPB / K2_TPB);
     if (ep_grid == 0) ep_grid = 1;
@@ -339,7 +346,7 @@ static hipError_t launch_pipeline(const LaunchArgs &a, uint64_t *parts)
         if (L.k2_kind == 0) hipLaunchKernelGGL((msim_episode_kernel<M, 0>), dim3(ep_grid), dim3(K2_TPB), 0, a.stream, a.p, pa);
         else if (L.k2_kind == 1) hipLaunchKernelGGL((msim_episode_kernel<M, 1>), dim3(ep_grid), dim3(K2_TPB), 0, a.stream, a.p, pa);
         else hipLaunchKernelGGL((msim_episode_kernel<M, 2>), dim3(ep_grid), dim3(K2_TPB), 0, a.stream, a.p, pa);
-        hipLaunchKernelGGL((msim_combine_kernel<M>), dim3((cn + K3_TPB - 1) / K3_TPB), dim3(K3_TPB), 0, a.stream, a.p, pa,
+        hipLaunchKernelGGL((msim_combine_kernel<M>), dim3((cn + K3_TPB - 1) / K3_TPB), dim3(K3_TPB), 0, a.stream, a.p, pk3,
                            cn, off, parts + (size_t)(off / K3_TPB) * 6 * M, a.records, a.best_h, a.err_count, a.err_list,
                            a.err_cap);
     }

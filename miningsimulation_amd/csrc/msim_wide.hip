@@ -581,14 +581,16 @@ static uint32_t wide_w1_runs_uncached(uint32_t m)
             bw = w[i];
             best = 1u << i;
         }
-    if (const char *e = getenv("MSIM_W1_RUNS")) {  // A/B override: 1, 2, 4 or 8 runs, when its LDS fits
-        const uint32_t r = (uint32_t)atoi(e);
-        if ((r == 1 || r == 2 || r == 4 || r == 8) && wide_w1_lds(m, r) <= 150 * 1024) best = r;
-    }
     return best;
 }
 uint32_t wide_w1_runs(uint32_t m)
 {
+    // A/B override: 1, 2, 4 or 8 runs, when its LDS fits. Read on every launch, not cached with the occupancy
+    // choice: a process that changes it between launches (the tests do) gets what it asked for.
+    if (const char *e = getenv("MSIM_W1_RUNS")) {
+        const uint32_t r = (uint32_t)atoi(e);
+        if ((r == 1 || r == 2 || r == 4 || r == 8) && wide_w1_lds(m, r) <= 150 * 1024) return r;
+    }
     static std::mutex mu;
     static std::map<std::pair<int, uint32_t>, uint32_t> cache;
     int dev = 0;

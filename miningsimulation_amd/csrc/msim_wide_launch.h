@@ -54,8 +54,10 @@ struct WideLayout {
     size_t hist_off, info_off, tlast_off, lanes_off, cand_off, recs_off, work_off, retry_off, counts_off, total;
 };
 
-// rho = P(a block is not fast) = sum_k w_k/W * P(I <= prop_k).
-inline WideLayout wide_layout_for(double rho, uint32_t m, int64_t duration_ms, uint64_t n_runs, double budget)
+// rho = P(a block is not fast) = sum_k w_k/W * P(I <= prop_k). max_nr (a multiple of 256; 0: none) caps the runs
+// per slice below what the budget allows (test switch MSIM_MAX_SLICE_RUNS, msim_api.hip).
+inline WideLayout wide_layout_for(double rho, uint32_t m, int64_t duration_ms, uint64_t n_runs, double budget,
+                                  uint32_t max_nr = 0)
 {
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     WideLayout L;
@@ -69,6 +71,7 @@ inline WideLayout wide_layout_for(double rho, uint32_t m, int64_t duration_ms, u
                            L.rcap * (sizeof(WideCand) + 4.0 * WREC_WORDS + 8.0) + 64;
     uint64_t cap = (uint64_t)(budget / per_run) / 256 * 256;
     if (cap < 256) cap = 256;
+    if (max_nr && max_nr < cap) cap = max_nr;
     const uint64_t want = (n_runs + 3) / 4 * 4;
     L.nr = (uint32_t)(want < cap ? want : cap);
     size_t o = 0;

@@ -54,6 +54,8 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB)
         L.oracle_run.argtypes = [ctypes.POINTER(OMiner), ctypes.c_int, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32,
                                  ctypes.POINTER(ORunStats), ctypes.POINTER(OTrace)]
+        L.oracle_run_w.argtypes = [ctypes.POINTER(OMiner), ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32,
+                                   ctypes.c_uint32, ctypes.POINTER(ORunStats), ctypes.POINTER(OTrace)]
         L.oracle_run_batch.argtypes = [ctypes.POINTER(OMiner), ctypes.c_int, ctypes.c_int64, ctypes.c_uint64,
                                        ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ORunStats),
                                        ctypes.POINTER(OSum)]
@@ -99,13 +101,16 @@ def _miners(percs: Sequence[int], props: Sequence[int], selfish: Sequence[bool],
     return arr
 
 
-def run(percs, props, selfish, duration_ms: int, seed_interval: int, seed_picker: int) -> Tuple[int, np.ndarray]:
-    """One RunSimulation: returns (rc, array [M, 2] of (blocks_found, stale_blocks)) plus best length via trace."""
+def run(percs, props, selfish, duration_ms: int, seed_interval: int, seed_picker: int,
+        total_weight: int = 100) -> Tuple[int, np.ndarray]:
+    """One RunSimulation: returns (rc, array [M, 2] of (blocks_found, stale_blocks)) plus best length via trace.
+
+    total_weight != 100: `percs` are integer weights summing to it (as run_batch)."""
     m = len(percs)
     out = (ORunStats * m)()
     tr = OTrace()
-    rc = lib().oracle_run(_miners(percs, props, selfish), m, duration_ms, seed_interval & 0xFFFFFFFF,
-                          seed_picker & 0xFFFFFFFF, out, ctypes.byref(tr))
+    rc = lib().oracle_run_w(_miners(percs, props, selfish), m, duration_ms, total_weight, seed_interval & 0xFFFFFFFF,
+                            seed_picker & 0xFFFFFFFF, out, ctypes.byref(tr))
     res = np.array([[out[k].blocks_found, out[k].stale_blocks] for k in range(m)], dtype=np.int64)
     return rc, res, int(tr.best_len) - 1
 
