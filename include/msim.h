@@ -119,7 +119,10 @@ uint32_t msim_config_miner_count(const msim_config *cfg);
 /* Run runs [run_begin, run_begin + n_runs) on HIP device `device`.
  * out_sums: M entries (like stats_total, main.cpp:199); with opt_per_run given, the share/stale_rate
  *           doubles are summed on the host in run order exactly as main.cpp:211-217 does; otherwise
- *           they come from the fixed-point device sums (relative error < 1e-9).
+ *           they come from the fixed-point device sums (relative error < 1e-9: that bounds the fixed-point
+ *           aggregate against the run-order f64 sum, i.e. the per-run rounding to 2^-32 and the summation
+ *           order; the device sums themselves equal their definition, the integer sum of the per-run terms
+ *           round(x * 2^32), exactly, on every engine).
  * opt_per_run: n_runs * M records or NULL; opt_best_height: n_runs entries (|best chain| - 1) or NULL.
  * opt_sums: M fixed-point msim_sums or NULL. */
 int msim_run(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,

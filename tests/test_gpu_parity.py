@@ -2,13 +2,16 @@
 
 Bar: bit-exact per-run integer counters (found, stale, best-chain height) for identical seeds; f64
 aggregates from per-run records bit-exact against the oracle's run-order sums (main.cpp:211-217);
-fixed-point device sums within 1e-9 relative of those; sizes where the oracle cannot follow are checked
+fixed-point device sums equal, integer for integer, to the per-run terms rebuilt from the oracle's counters
+(tests/sums_reference.py); sizes where the oracle cannot follow are checked
 through size-independent invariants."""
 import os
 import random
 
 import numpy as np
 import pytest
+
+import sums_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -118,11 +121,11 @@ def test_gpu_presets_vs_oracle(msim, oracle, preset):
         assert res.stats_total[k].blocks_found == int(f[:, k].sum())
         assert res.stats_total[k].blocks_share == ref_share
         assert res.stats_total[k].stale_rate == ref_rate
-        # fixed-point device sums
-        fx = msim.sums_to_stats([[res.sums[k].blocks_found, res.sums[k].stale_blocks, res.sums[k].share_hi,
-                                  res.sums[k].share_lo, res.sums[k].rate_hi, res.sums[k].rate_lo]])[0]
-        assert abs(fx.blocks_share - ref_share) <= 1e-9 * max(1.0, ref_share)
-        assert abs(fx.stale_rate - ref_rate) <= 1e-9 * max(1.0, ref_rate) + n * 2.0**-32
+    # fixed-point device sums: exactly the per-run terms rebuilt from the oracle's counters (tests/sums_reference.py)
+    want = sums_reference.expected(f, st, f.sum(axis=1))
+    assert want == sums_reference.expected_from_doubles(f, st, sh, r)
+    bad = sums_reference.diff(sums_reference.combined(res.sums), want)
+    assert not bad, (preset, bad[:8])
 
 
 def test_gpu_random_networks(msim, oracle):
