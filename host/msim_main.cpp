@@ -17,12 +17,18 @@
 //         "grid": {"selfish_perc": [..], "propagation_ms": [..]}}            or
 //         "points": [{"miners": [{"id": 0, "perc": 40, "propagation_ms": 1000, "selfish": true}, ..]}, ..]}
 //
+// --errors (anywhere on the command line): per-miner standard errors from the exact on-device second moments
+// (msim_run_moments / msim_sweep_run_moments, one GPU): " ± .." columns after each report line ("n/a" where a
+// standard error is undefined, i.e. for a single run) and an "errors" object per miner in --json output.
+// Without the flag the output is unchanged.
+//
 // Build: make -C host
 // "c5" runs BASELINE configs[4] (2 pools + 1 024 small miners, integer weights summing to
 // W = 102 400, msim_config_create_weighted), which the reference's integer percentages cannot express.
 #include <unistd.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -93,9 +99,18 @@ static int die(const char *what, int rc)
     return 1;
 }
 
-// main.cpp:224-234 for one network.
+// A standard error as the report prints its means (%g), "n/a" for NaN.
+static std::string PlusMinus(double se, double scale, const char *unit)
+{
+    if (std::isnan(se)) return "n/a";
+    char buf[64];
+    std::snprintf(buf, sizeof(buf), "%g%s", se * scale, unit);
+    return buf;
+}
+
+// main.cpp:224-234 for one network; with `errors` (--errors) the standard errors of the three means follow each line.
 static void PrintReport(const std::vector<Miner> &miners, const std::vector<msim_stats> &stats_total, uint64_t runs,
-                        uint64_t total_weight, long long days)
+                        uint64_t total_weight, long long days, const msim_errors *errors = nullptr)
 {
     std::printf("After running %llu simulations for %lldd each, on average:\n", (unsigned long long)runs, days);
     for (size_t i = 0; i < miners.size(); ++i) {
@@ -110,23 +125,48 @@ static void PrintReport(const std::vector<Miner> &miners, const std::vector<msim
         std::printf("%g%% of blocks. Stale rate: %g%%.", stats.blocks_share * 100 / (double)runs,
                     stats.stale_rate * 100 / (double)runs);
         if (miner.is_selfish) std::printf(" ('selfish mining' strategy)");
+        if (errors)
+            std::printf(" ± %s blocks, ± %s of blocks, stale rate ± %s", PlusMinus(errors[i].found_se, 1.0, "").c_str(),
+                        PlusMinus(errors[i].share_se, 100.0, "%").c_str(), PlusMinus(errors[i].rate_se, 100.0, "%").c_str());
         std::printf("\n");
     }
 }
 
 // One JSON line for a point: the network and its per-miner averages (the report's numbers).
+static void PrintJsonNumber(const char *sep, const char *name, double v)
+{
+    if (std::isnan(v))
+        std::printf("%s\"%s\": null", sep, name);
+    else
+        std::printf("%s\"%s\": %.17g", sep, name, v);
+}
+
 static void PrintJson(size_t point, const std::vector<Miner> &miners, const std::vector<msim_stats> &st, uint64_t runs,
-                      uint64_t total_weight)
+                      uint64_t total_weight, const msim_errors *errors = nullptr)
 {
     std::printf("{\"point\": %zu, \"runs\": %llu, \"total_weight\": %llu, \"miners\": [", point,
                 (unsigned long long)runs, (unsigned long long)total_weight);
-    for (size_t i = 0; i < miners.size(); ++i)
+    for (size_t i = 0; i < miners.size(); ++i) {
         std::printf("%s{\"id\": %u, \"perc\": %llu, \"propagation_ms\": %lld, \"selfish\": %s, "
-                    "\"blocks_found\": %.17g, \"blocks_share\": %.17g, \"stale_rate\": %.17g}",
+                    "\"blocks_found\": %.17g, \"blocks_share\": %.17g, \"stale_rate\": %.17g",
                     i ? ", " : "", miners[i].id, (unsigned long long)miners[i].perc,
                     (long long)miners[i].propagation.count(), miners[i].is_selfish ? "true" : "false",
                     (double)st[i].blocks_found / (double)runs, st[i].blocks_share / (double)runs,
                     st[i].stale_rate / (double)runs);
+        if (errors) {
+            const msim_errors &e = errors[i];
+            PrintJsonNumber(", \"errors\": {", "found_mean", e.found_mean);
+            PrintJsonNumber(", ", "found_se", e.found_se);
+            PrintJsonNumber(", ", "share_mean", e.share_mean);
+            PrintJsonNumber(", ", "share_se", e.share_se);
+            PrintJsonNumber(", ", "rate_mean", e.rate_mean);
+            PrintJsonNumber(", ", "rate_se", e.rate_se);
+            PrintJsonNumber(", ", "pooled_rate", e.pooled_rate);
+            PrintJsonNumber(", ", "pooled_rate_se", e.pooled_rate_se);
+            std::printf("}");
+        }
+        std::printf("}");
+    }
     std::printf("]}\n");
 }
 
@@ -172,6 +212,7 @@ struct SweepSpec {
     uint64_t total_weight = 100;
     int gpus = 1;
     bool json = false;
+    bool errors = false;
 };
 
 static void AddGrid(SweepSpec &sp, const std::vector<int64_t> &hs, const std::vector<int64_t> &props)
@@ -230,19 +271,29 @@ static int RunSweep(const SweepSpec &sp)
     if (rc == MSIM_OK) rc = msim_sweep_create(cfgs.data(), (uint32_t)cfgs.size(), &sw);
     const uint32_t m = cfgs.empty() ? 0 : msim_config_miner_count(cfgs[0]);
     std::vector<msim_stats> st(sp.points.size() * m);
-    if (rc == MSIM_OK)
+    std::vector<msim_errors> errs;
+    if (rc == MSIM_OK && sp.errors) {
+        std::vector<msim_moments> mo(st.size());
+        errs.resize(st.size());
+        rc = WithStdoutOnStderr([&] {
+            return msim_sweep_run_moments(sw, 0, sp.runs, sp.seed_base, 0, st.data(), nullptr, mo.data(), nullptr, nullptr);
+        });
+        if (rc == MSIM_OK) msim_moments_to_errors(mo.data(), (uint32_t)mo.size(), sp.runs, errs.data());
+    } else if (rc == MSIM_OK) {
         rc = WithStdoutOnStderr([&] {
             return msim_sweep_run_multi(sw, 0, sp.runs, sp.seed_base, nullptr, (uint32_t)sp.gpus, st.data(), nullptr);
         });
+    }
     if (rc == MSIM_OK) {
         const long long days = sp.duration_ms / 86'400'000;
         for (size_t p = 0; p < sp.points.size(); ++p) {
             const std::vector<msim_stats> ps(st.begin() + p * m, st.begin() + (p + 1) * m);
+            const msim_errors *pe = sp.errors ? errs.data() + p * m : nullptr;
             if (sp.json) {
-                PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight);
+                PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe);
             } else {
                 std::printf("Point %zu of %zu:\n", p + 1, sp.points.size());
-                PrintReport(sp.points[p], ps, sp.runs, sp.total_weight, days);
+                PrintReport(sp.points[p], ps, sp.runs, sp.total_weight, days, pe);
             }
         }
     }
@@ -253,6 +304,17 @@ static int RunSweep(const SweepSpec &sp)
 
 int main(int argc, char **argv)
 {
+    bool errors = false;  // --errors, wherever it stands; the other arguments keep their positions
+    {
+        int kept = 1;
+        for (int i = 1; i < argc; ++i) {
+            if (std::string(argv[i]) == "--errors")
+                errors = true;
+            else
+                argv[kept++] = argv[i];
+        }
+        argc = kept;
+    }
     if (argc > 1 && (std::string(argv[1]) == "--grid" || std::string(argv[1]) == "--sweep")) {
         SweepSpec sp;
         try {
@@ -273,6 +335,7 @@ int main(int argc, char **argv)
                 else if (a == "--seed" && i + 1 < argc) sp.seed_base = (uint32_t)std::stoul(argv[++i]);
                 else throw std::runtime_error("unknown option " + a);
             }
+            sp.errors = errors;
         } catch (const std::exception &e) {
             std::fprintf(stderr, "msim_main: %s\n", e.what());
             return 2;
@@ -295,14 +358,25 @@ int main(int argc, char **argv)
     // main.cpp:201 (the reference names its thread count; here one stream drives each GPU)
     std::printf("Running %d simulations in parallel using %d threads.\n", SIM_RUNS, n_gpus);
     std::vector<msim_stats> stats_total(miners.size());
-    if (int rc = WithStdoutOnStderr([&] {
-            return msim_run_multi(cfg, 0, SIM_RUNS, seed_base, nullptr, (uint32_t)n_gpus, stats_total.data(), nullptr);
-        }))
+    std::vector<msim_errors> errs;
+    if (errors) {
+        std::vector<msim_moments> mo(miners.size());
+        errs.resize(miners.size());
+        if (int rc = WithStdoutOnStderr([&] {
+                return msim_run_moments(cfg, 0, SIM_RUNS, seed_base, 0, stats_total.data(), nullptr, mo.data(), nullptr,
+                                        nullptr);
+            }))
+            return die("msim_run_moments", rc);
+        msim_moments_to_errors(mo.data(), (uint32_t)mo.size(), SIM_RUNS, errs.data());
+    } else if (int rc = WithStdoutOnStderr([&] {
+                   return msim_run_multi(cfg, 0, SIM_RUNS, seed_base, nullptr, (uint32_t)n_gpus, stats_total.data(),
+                                         nullptr);
+               }))
         return die("msim_run_multi", rc);
     std::printf("\r100%% progress..\n");  // main.cpp:219-221
 
     const auto days{std::chrono::duration_cast<std::chrono::days>(SIM_DURATION)};
-    PrintReport(miners, stats_total, SIM_RUNS, total_weight, (long long)days.count());
+    PrintReport(miners, stats_total, SIM_RUNS, total_weight, (long long)days.count(), errors ? errs.data() : nullptr);
     msim_config_destroy(cfg);
     return 0;
 }

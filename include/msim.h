@@ -105,7 +105,10 @@ int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t du
  * entry points all follow it; the general engine has no slices. Unset, nothing changes.
  * A third, MSIM_PIPE_FORCE_RETRY (set to anything), read at every launch of the honest pipeline: its combine
  * kernel flags every run, so the retry kernel computes them all (what MSIM_SEL_FORCE_RETRY does on the entity
- * engine); at most 65 536 runs per launch then, the retry list's size. */
+ * engine); at most 65 536 runs per launch then, the retry list's size.
+ * A fourth, MSIM_MOMENTS_CHUNK_RUNS=<n> (n > 0), read only by msim_run_moments and msim_sweep_run_moments at every
+ * call: a chunk of runs whose records stay in device memory holds at most n runs (per point), so a few hundred
+ * runs exercise the chunk loop and its limb-by-limb addition. */
 int msim_config_is_wide(const msim_config *cfg);
 /* How many launches of this config the caller keeps in flight at once (default 1; e.g. 2 when steps
  * alternate over two HIP streams). The event-skipping pipeline plans its draw kernel's grid for it: three
@@ -252,6 +255,72 @@ typedef struct msim_interval_moments {
 } msim_interval_moments;
 int msim_sample_picks(const msim_config *cfg, uint64_t seed, uint64_t n, uint64_t *out_counts, int device);
 int msim_sample_intervals(uint64_t seed, uint64_t n, msim_interval_moments *out, int device);
+
+/* Per-miner error bars: exact second moments and histograms of the per-run terms, reduced on the device from the
+ * records a launch writes on request (d_per_run, d_best_height). For one run and one miner, with f = record.found,
+ * s = record.stale and L = best_height[run], the terms are the ones every engine adds to its msim_sums:
+ *   share_t = (f == 0 || L == 0) ? 0 : (uint64)((double)f / (double)L * 2^32 + 0.5)
+ *   rate_t  = (f == 0)           ? 0 : (uint64)((double)s / (double)f * 2^32 + 0.5)
+ * (L == 0 with f > 0 only happens to a miner holding Genesis's id, simulation.h:31-33, in a run without blocks;
+ * the engines' own share term f / 0 has no value there, and `first` counts 0 for it.)
+ * Every field is a plain integer sum over runs, so it is identical for any split into workgroups, launches or
+ * ranks and can be all-reduced. `first` follows msim_sums' limb convention. A square sum holds, in limb i, the sum
+ * of the i-th 32-bit pieces of the runs' full 128-bit (64-bit for found/stale) products: its value is
+ * sum(limb[i] << 32 i), limbs are not normalised (join them with carries), exact up to 2^32 runs. */
+typedef struct msim_moments {
+    msim_sums first;         /* recomputed from the records */
+    uint64_t found_sq[2];    /* sum f^2 */
+    uint64_t stale_sq[2];    /* sum s^2 */
+    uint64_t found_stale[2]; /* sum f s */
+    uint64_t share_sq[4];    /* sum share_t^2 */
+    uint64_t rate_sq[4];     /* sum rate_t^2 */
+} msim_moments;
+
+/* Histograms of the terms, bin widths powers of two in term units (2^-32):
+ *   bin(t) = 0 if t < lo;  bins + 1 if ((t - lo) >> shift) >= bins;  1 + ((t - lo) >> shift) otherwise.
+ * Counts are uint64 [points][M][2][bins + 2], index 0 = share, 1 = rate; every row adds up to the run count. */
+typedef struct msim_hist_spec {
+    uint32_t bins; /* 1..1024 */
+    uint32_t share_shift, rate_shift; /* 0..63 */
+    uint64_t share_lo, rate_lo;
+} msim_hist_spec;
+
+/* Device-resident and asynchronous on `stream` (hipStream_t, NULL = default): no allocation, no synchronisation,
+ * independent of any config. d_per_run: n_points * runs_per_point * m msim_run_record and d_best_height:
+ * n_points * runs_per_point uint32_t, in msim_launch's / msim_sweep_launch's layouts (device memory). d_moments:
+ * n_points * m msim_moments, and d_hist_or_NULL (with opt_hist_spec): the counts above; both are overwritten
+ * (zeroed inside the launch, as d_sums is). Results are meaningless for a launch whose d_status[1] != 0: a failed
+ * run writes no record. MSIM_E_INVALID for m == 0, no runs, more than 2^32 - 1 runs per point, bins outside
+ * 1..1024, a shift above 63, or exactly one of opt_hist_spec / d_hist_or_NULL. */
+int msim_moments_launch(uint32_t m, uint32_t n_points, uint64_t runs_per_point, const void *d_per_run,
+                        const void *d_best_height, const msim_hist_spec *opt_hist_spec, void *d_moments,
+                        void *d_hist_or_NULL, void *stream);
+/* Host conveniences shaped like msim_run / msim_sweep_run: the records and best heights stay in device memory,
+ * only sums, status, moments and histograms come back; chunks of runs are added limb by limb on the host.
+ * out_stats: from the fixed-point sums. out_moments: M (n_points * M) entries; opt_hist with opt_hist_spec:
+ * M * 2 * (bins + 2) (times n_points) counts, or both NULL. MSIM_E_CAPACITY on a failed run, as msim_run.
+ * A test switch, MSIM_MOMENTS_CHUNK_RUNS=<n> (n > 0), read only by these two functions: a chunk holds at most n
+ * runs (per point), so a few hundred runs exercise the chunk loop. */
+int msim_run_moments(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                     msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments,
+                     const msim_hist_spec *opt_hist_spec, uint64_t *opt_hist);
+int msim_sweep_run_moments(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base,
+                           int device, msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments,
+                           const msim_hist_spec *opt_hist_spec, uint64_t *opt_hist);
+
+/* Means and standard errors per miner from the moments of N = n_runs runs: mean = S1 / N and
+ * se = sqrt((N S2 - S1^2) / (N^2 (N - 1))), share and rate scaled by 2^-32. pooled_rate = sum s / sum f (0 when
+ * sum f = 0) with its delta-method error sqrt(N / (N - 1) (F^2 sum s^2 - 2 S F sum fs + S^2 sum f^2)) / F^2
+ * (0 when F = 0). The integer numerators are formed exactly, then a handful of correctly rounded f64 operations
+ * follow, so differently normalised limbs of one value give the same bits. Every *_se is NaN for N == 1. */
+typedef struct msim_errors {
+    double found_mean, found_se;
+    double share_mean, share_se;
+    double rate_mean, rate_se;
+    double pooled_rate, pooled_rate_se;
+} msim_errors;
+/* Host only. */
+void msim_moments_to_errors(const msim_moments *moments, uint32_t m, uint64_t n_runs, msim_errors *out);
 
 /* Convert fixed-point sums to MinerStats-style doubles. */
 void msim_sums_to_stats(const msim_sums *sums, uint32_t n, msim_stats *out);

@@ -31,6 +31,14 @@ from .simulation import (  # noqa: F401
     timing_read,
 )
 
+from .moments import (  # noqa: F401,E402
+    HistSpec,
+    error_bars,
+    errors_from_moments,
+    hist_quantile,
+    report_with_errors,
+)
+
 from . import model  # noqa: F401,E402  (first-order analytical stale-rate model, plot.py restated)
 
 __version__ = "0.1.0"

@@ -58,6 +58,10 @@ EXPORTED = (
     "msim_version",
     "msim_sample_picks",
     "msim_sample_intervals",
+    "msim_moments_launch",
+    "msim_run_moments",
+    "msim_sweep_run_moments",
+    "msim_moments_to_errors",
 )
 
 
@@ -116,6 +120,23 @@ class MsimError(RuntimeError):
 class MsimIntervalMoments(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint64), ("sum", ctypes.c_uint64), ("sumsq_lo", ctypes.c_uint64),
                 ("sumsq_hi", ctypes.c_uint64), ("max", ctypes.c_uint64)]
+
+
+class MsimMoments(ctypes.Structure):
+    """msim_moments: 20 uint64 per miner, every field a plain sum over runs (limbs not normalised)."""
+    _fields_ = [("first", MsimSums), ("found_sq", ctypes.c_uint64 * 2), ("stale_sq", ctypes.c_uint64 * 2),
+                ("found_stale", ctypes.c_uint64 * 2), ("share_sq", ctypes.c_uint64 * 4),
+                ("rate_sq", ctypes.c_uint64 * 4)]
+
+
+class MsimHistSpec(ctypes.Structure):
+    _fields_ = [("bins", ctypes.c_uint32), ("share_shift", ctypes.c_uint32), ("rate_shift", ctypes.c_uint32),
+                ("share_lo", ctypes.c_uint64), ("rate_lo", ctypes.c_uint64)]
+
+
+class MsimErrors(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("found_mean", "found_se", "share_mean", "share_se", "rate_mean",
+                                               "rate_se", "pooled_rate", "pooled_rate_se")]
 
 
 def _load() -> ctypes.CDLL:
@@ -198,6 +219,16 @@ def _load() -> ctypes.CDLL:
     lib.msim_sample_picks.restype = ctypes.c_int
     lib.msim_sample_intervals.argtypes = [u64, u64, ctypes.POINTER(MsimIntervalMoments), ctypes.c_int]
     lib.msim_sample_intervals.restype = ctypes.c_int
+    lib.msim_moments_launch.argtypes = [u32, u32, u64, vp, vp, ctypes.POINTER(MsimHistSpec), vp, vp, vp]
+    lib.msim_moments_launch.restype = ctypes.c_int
+    lib.msim_run_moments.argtypes = [vp, u64, u64, u32, ctypes.c_int, ctypes.POINTER(MsimStats),
+                                     ctypes.POINTER(MsimSums), ctypes.POINTER(MsimMoments),
+                                     ctypes.POINTER(MsimHistSpec), ctypes.POINTER(u64)]
+    lib.msim_run_moments.restype = ctypes.c_int
+    lib.msim_sweep_run_moments.argtypes = lib.msim_run_moments.argtypes
+    lib.msim_sweep_run_moments.restype = ctypes.c_int
+    lib.msim_moments_to_errors.argtypes = [ctypes.POINTER(MsimMoments), u32, u64, ctypes.POINTER(MsimErrors)]
+    lib.msim_moments_to_errors.restype = None
     lib.msim_version.argtypes = []
     lib.msim_version.restype = ctypes.c_char_p
     return lib

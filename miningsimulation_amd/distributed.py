@@ -107,3 +107,74 @@ def run_sharded(sim, n_total: int, seed_base: int, run_begin: int = 0, stream=No
     if int(status[1].item()) != 0:
         raise RuntimeError(f"{int(status[1].item())} runs exceeded the compact state capacity")
     return sums
+
+
+def run_sharded_moments(sim, n_total: int, seed_base: int, run_begin: int = 0, stream=None,
+                        launch: Optional[Callable] = None, launch_moments: Optional[Callable] = None, device=None,
+                        max_chunk: int = MAX_LAUNCH_RUNS, hist=None):
+    """run_sharded plus the second moments (and, with a HistSpec `hist`, the histograms) of the per-run terms:
+    every chunk runs msim_launch with device-resident records and then msim_moments_launch on the launch stream,
+    and sums, status, moments and histogram travel in ONE int64 buffer with ONE all-reduce. All of them are
+    integer sums over runs, so the result is bit-identical for every world size and partition.
+
+    Returns a SimulationResult (stats_total, sums, moments, hist, n_runs = n_total), identical on every rank.
+    `launch` / `launch_moments` replace sim.launch / sim.launch_moments (same signatures, workspace None) so
+    that the partition, chunking, packing and all-reduce can be exercised on CPU ranks with a gloo group."""
+    import contextlib
+
+    import torch
+    import torch.distributed as dist
+
+    from ._lib import MsimSums
+    from .moments import MOMENT_WORDS, moments_from_words
+    from .simulation import SimulationResult, sums_to_stats
+
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    begin, n = shard(n_total, world, rank)
+    m = len(sim.miners)
+    row = hist.bins + 2 if hist is not None else 0
+    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    o_status, o_mom, o_hist = 6 * m, 6 * m + 2, 6 * m + 2 + MOMENT_WORDS * m
+    buf = torch.zeros(o_hist + 2 * row * m, dtype=torch.int64, device=dev)
+    part = torch.zeros((m, 6), dtype=torch.int64, device=dev)
+    pst = torch.zeros(2, dtype=torch.int32, device=dev)
+    pmom = torch.zeros((m, MOMENT_WORDS), dtype=torch.int64, device=dev)
+    phist = torch.zeros((m, 2, row), dtype=torch.int64, device=dev) if hist is not None else None
+    chunk = min(n, max_chunk)
+    rec = torch.zeros((max(chunk, 1), m, 2), dtype=torch.int32, device=dev)
+    bh = torch.zeros(max(chunk, 1), dtype=torch.int32, device=dev)
+    ws = None
+    if n and launch is None:
+        ws = torch.empty(sim.workspace_bytes(chunk), dtype=torch.uint8, device=dev)
+    # as in run_sharded: everything that touches the launches' outputs runs on the launch stream
+    ctx = torch.cuda.stream(stream) if (stream is not None and dev.type == "cuda") else contextlib.nullcontext()
+    if stream is not None and dev.type == "cuda":
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    with ctx:
+        for off in range(0, n, max(chunk, 1)):
+            cn = min(chunk, n - off)
+            (launch or sim.launch)(cn, run_begin + begin + off, seed_base, part, ws, pst, d_per_run=rec,
+                                   d_best_height=bh, stream=stream)
+            (launch_moments or sim.launch_moments)(cn, rec, bh, pmom, hist, phist, stream=stream)
+            buf[:o_status] += part.view(-1)
+            buf[o_status:o_mom] += pst
+            buf[o_mom:o_hist] += pmom.view(-1)
+            if hist is not None:
+                buf[o_hist:] += phist.view(-1)
+        if world > 1:
+            dist.all_reduce(buf)
+    if stream is not None and dev.type == "cuda":
+        torch.cuda.current_stream(dev).wait_stream(stream)
+    host = buf.cpu()
+    if int(host[o_status + 1]) != 0:
+        raise RuntimeError(f"{int(host[o_status + 1])} runs exceeded the compact state capacity")
+    rows = host[:o_status].view(m, 6).tolist()
+    u64 = (lambda v: int(v) & 0xFFFFFFFFFFFFFFFF)
+    return SimulationResult(
+        stats_total=sums_to_stats([[u64(x) for x in r] for r in rows]),
+        sums=[MsimSums(r[0], r[1], u64(r[2]), u64(r[3]), u64(r[4]), u64(r[5])) for r in rows],
+        n_runs=n_total,
+        moments=moments_from_words(host[o_mom:o_hist].view(m, MOMENT_WORDS).numpy()),
+        hist=host[o_hist:].view(m, 2, row).numpy().astype("uint64") if hist is not None else None,
+    )

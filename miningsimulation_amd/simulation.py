@@ -20,7 +20,8 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import MsimMiner, MsimRunRecord, MsimStats, MsimSums, MsimTiming, check, lib
+from ._lib import MsimMiner, MsimMoments, MsimRunRecord, MsimStats, MsimSums, MsimTiming, check, lib
+from .moments import MOMENT_WORDS, HistSpec, moments_from_words
 
 SIM_DURATION_MS = 31_556_952_000  # main.cpp:7 std::chrono::months{12}
 SIM_RUNS = 16 * 2048              # main.cpp:10
@@ -104,6 +105,47 @@ class SimulationResult:
     best_height: Optional[np.ndarray] = None    # [n_runs] uint32, |best chain| - 1
     n_runs: int = 0
     extra: dict = field(default_factory=dict)
+    moments: Optional[list] = None              # per-miner dicts of Python ints (moments.join_limbs): run_moments
+    hist: Optional[np.ndarray] = None           # [M, 2, bins + 2] uint64 counts (0 = share, 1 = rate), or None
+
+
+def _launch_moments(m: int, n_points: int, runs_per_point: int, d_per_run, d_best_height, d_moments,
+                    hist_spec: Optional[HistSpec], d_hist, stream) -> None:
+    ptr = (lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None)
+    sh = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    if (hist_spec is None) != (d_hist is None):
+        raise ValueError("hist_spec and d_hist go together")
+    need = n_points * runs_per_point
+    if (d_per_run.numel() * d_per_run.element_size() < need * m * 8 or
+            d_best_height.numel() * d_best_height.element_size() < need * 4 or
+            d_moments.numel() * d_moments.element_size() < n_points * m * MOMENT_WORDS * 8 or
+            (d_hist is not None and
+             d_hist.numel() * d_hist.element_size() < n_points * m * 2 * (hist_spec.bins + 2) * 8)):
+        raise ValueError("a buffer is smaller than the launch reads or writes")
+    spec = ctypes.byref(hist_spec.struct()) if hist_spec is not None else None
+    check(lib.msim_moments_launch(m, n_points, runs_per_point, ptr(d_per_run), ptr(d_best_height), spec,
+                                  ptr(d_moments), ptr(d_hist), sh), "msim_moments_launch")
+
+
+def _run_moments(fn, what: str, handle, n_points: int, m: int, n_runs: int, run_begin: int, seed_base: int,
+                 device: int, hist: Optional[HistSpec]) -> List[SimulationResult]:
+    nm = n_points * m
+    stats = (MsimStats * nm)()
+    sums = (MsimSums * nm)()
+    mom = (MsimMoments * nm)()
+    row = hist.bins + 2 if hist is not None else 0
+    counts = (ctypes.c_uint64 * (nm * 2 * row))() if hist is not None else None
+    spec = ctypes.byref(hist.struct()) if hist is not None else None
+    check(fn(handle, run_begin, n_runs, seed_base & 0xFFFFFFFF, device, stats, sums, mom, spec, counts), what)
+    words = np.ctypeslib.as_array(ctypes.cast(mom, ctypes.POINTER(ctypes.c_uint64)), shape=(nm, MOMENT_WORDS))
+    h = np.ctypeslib.as_array(counts).reshape(n_points, m, 2, row).copy() if hist is not None else None
+    return [SimulationResult(
+        stats_total=[MinerStats(s.blocks_found, s.blocks_share, s.stale_rate) for s in stats[p * m:(p + 1) * m]],
+        sums=list(sums[p * m:(p + 1) * m]),
+        n_runs=n_runs,
+        moments=moments_from_words(words[p * m:(p + 1) * m]),
+        hist=h[p] if h is not None else None,
+    ) for p in range(n_points)]
 
 
 def _miners_struct(miners: Sequence[Miner]):
@@ -171,6 +213,20 @@ class Simulation:
             res.stale = a[:, :, 1]
             res.best_height = np.ctypeslib.as_array(bh).copy()
         return res
+
+    def run_moments(self, n_runs: int, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE, device: int = 0,
+                    hist: Optional[HistSpec] = None) -> SimulationResult:
+        """msim_run_moments: run() plus the exact second moments of the per-run terms (`moments`) and, with a
+        HistSpec, their histograms (`hist`); the per-run records never leave device memory. error_bars(result)
+        turns the moments into standard errors."""
+        return _run_moments(lib.msim_run_moments, "msim_run_moments", self._h, 1, len(self.miners), n_runs, run_begin,
+                            seed_base, device, hist)[0]
+
+    def launch_moments(self, n_runs: int, d_per_run, d_best_height, d_moments, hist_spec: Optional[HistSpec] = None,
+                       d_hist=None, stream=None) -> None:
+        """msim_moments_launch on the current device over a launch's records: d_per_run int32 [n_runs, M, 2],
+        d_best_height int32 [n_runs], d_moments int64 [M, 20] and d_hist int64 [M, 2, bins + 2] (overwritten)."""
+        _launch_moments(len(self.miners), 1, n_runs, d_per_run, d_best_height, d_moments, hist_spec, d_hist, stream)
 
     def run_multi(self, n_runs: int, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
                   devices: Sequence[int] = (0,)) -> SimulationResult:
@@ -298,6 +354,18 @@ class Sweep:
                 res.best_height = np.ctypeslib.as_array(bh).reshape(n, runs_per_point)[p].copy()
             out.append(res)
         return out
+
+    def run_moments(self, runs_per_point: int, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
+                    device: int = 0, hist: Optional[HistSpec] = None) -> List[SimulationResult]:
+        """msim_sweep_run_moments: run() plus per-point `moments` and (with a HistSpec) `hist`."""
+        return _run_moments(lib.msim_sweep_run_moments, "msim_sweep_run_moments", self._h, len(self.sims), self.m,
+                            runs_per_point, run_begin, seed_base, device, hist)
+
+    def launch_moments(self, runs_per_point: int, d_per_run, d_best_height, d_moments,
+                       hist_spec: Optional[HistSpec] = None, d_hist=None, stream=None) -> None:
+        """msim_moments_launch over a sweep launch's records; d_moments int64 [n_points, M, 20]."""
+        _launch_moments(self.m, len(self.sims), runs_per_point, d_per_run, d_best_height, d_moments, hist_spec,
+                        d_hist, stream)
 
     def workspace_bytes(self, runs_per_point: int) -> int:
         return int(lib.msim_sweep_workspace_bytes(self._h, runs_per_point))
