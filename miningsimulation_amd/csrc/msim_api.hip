@@ -15,15 +15,40 @@
 #include <vector>
 
 #include "../../include/msim.h"
+#include "msim_devcache.h"
 #include "msim_general_launch.h"
+#include "msim_host.h"
 #include "msim_jump.h"
 #include "msim_kernels.h"
 #include "msim_sel_launch.h"
+#include "msim_timing.h"
 #include "msim_wide_launch.h"
 
-namespace {
-constexpr int MAX_DEVICES = 64;
-}
+using msim::align256;
+
+// The per-device table cache (msim_devcache.h) over HIP. A config or a sweep holds one, on its own mutex; the
+// keys name its tables.
+struct HipTables {
+    static bool device(int *dev) { return hipGetDevice(dev) == hipSuccess; }
+    static void *alloc(size_t bytes)
+    {
+        void *d = nullptr;
+        return hipMalloc(&d, bytes) == hipSuccess ? d : nullptr;
+    }
+    static bool upload(void *dst, const void *src, size_t bytes)
+    {
+        return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    static void release(void *ptr) { (void)hipFree(ptr); }
+};
+using TableCache = msim::DevCache<HipTables>;
+enum TableKey : uint64_t {
+    TAB_PIPE = 0,               // + segment length: pipeline tables; the entry's extent is its segment count
+    TAB_WIDE = 1ull << 32,      // pick, fast-threshold, prop, log, jump tables
+    TAB_SEL = 2ull << 32,       // SelParams of every point + point lists
+    TAB_GEN = 3ull << 32,       // GenParams of every point + arrays
+    TAB_POINTS = 4ull << 32,    // SimParams[n_points]
+};
 
 // A network as the general engine reads it (msim_general.h): integer weights summing to W.
 struct GenHost {
@@ -63,23 +88,16 @@ struct msim_config {
     bool pipe_ok;    // event-skipping pipeline eligible (honest network, rare forks)
     uint32_t jobs = 1;  // launches the caller keeps in flight at once (msim_config_set_concurrent_launches)
     std::mutex mu;
-    struct Tab {
-        int dev;
-        uint32_t seg, nseg;
-        void *ptr;
-    };
-    std::vector<Tab> tables;  // per (device, segment length) pipeline tables, lazily uploaded
+    TableCache tables{mu};  // per-device tables, lazily uploaded (TableKey)
     // Large honest networks (msim_wide.h): any miner count up to WIDE_MAX_M, integer weights summing to W.
     bool wide = false;
     uint64_t total_weight = 100;
     std::vector<uint32_t> wids;
     std::vector<uint64_t> wperc;
     std::vector<int64_t> wprop;
-    std::vector<std::pair<int, void *>> wtables;  // per device: pick, fast-threshold, prop, log, jump tables
     // Networks with selfish miners (msim_sel.h entity engine): parameter block.
     bool sel = false;
     msim::SelParams sp;
-    std::vector<std::pair<int, void *>> stables;  // per device: SelParams + point list {0}
     // The segment-parallel form of E1 (msim_selseg.h: SW workers + ST stitch) serves it when asked for
     // (MSIM_SELSEG): one selfish miner, the settled form applies, long runs, rare cuts (seg_rate: expected cuts
     // per find).
@@ -93,7 +111,6 @@ struct msim_config {
     bool general = false;
     bool selfish = false;   // some miner is selfish
     bool gen_full = false;  // G keeps its full last window tier (msim_general_launch.h gen_needs_full)
-    std::vector<std::pair<int, void *>> gtables;  // per device: GenParams + arrays
 };
 
 // A parameter sweep (BASELINE configs[3]): the points' parameter blocks, uploaded per device on first use.
@@ -102,7 +119,7 @@ struct msim_sweep {
     uint32_t m;
     bool self;
     std::mutex mu;
-    std::vector<std::pair<int, void *>> dev;  // (device, SimParams[n_points])
+    TableCache tables{mu};  // per-device tables, lazily uploaded (TableKey)
     // Entity-engine sweeps (some point has a selfish miner): every point's SelParams, the points grouped
     // by selfish class, one draw pass per slice shared by all points.
     bool sel = false;
@@ -113,12 +130,10 @@ struct msim_sweep {
         std::vector<uint32_t> points;
     };
     std::vector<Group> groups;
-    std::vector<std::pair<int, void *>> sdev;  // (device, SelParams[n_points] + point lists)
     // General-engine view of every point (G finishes what E2 cannot; a sweep with a general point runs on G)
     bool general = false;
     bool gen_full = false;  // some point needs G's full last window tier (gen_needs_full)
     std::vector<GenHost> gens;
-    std::vector<std::pair<int, void *>> gdev;  // (device, GenParams[n_points] + arrays)
 };
 
 namespace {
@@ -127,7 +142,7 @@ uint32_t err_cap_for(uint64_t n)
 {
     uint64_t c = n < 65536 ? n : 65536;
     if (c < 256) c = 256;
-    return (uint32_t)((c + 255) / 256 * 256);
+    return (uint32_t)align256(c);
 }
 
 struct WsLayout {
@@ -143,11 +158,9 @@ WsLayout ws_layout(uint32_t m, uint64_t n)
     l.counts_off = msim::partials_words(m, (uint32_t)n, l.err_cap) * sizeof(uint64_t);
     l.list_off = l.counts_off + 2 * sizeof(uint32_t);
     l.total = l.list_off + (size_t)l.err_cap * sizeof(uint32_t);
-    l.total = (l.total + 255) / 256 * 256;
+    l.total = align256(l.total);
     return l;
 }
-
-constexpr uint64_t MAX_LAUNCH_RUNS = 1ull << 26;
 
 // Sweep workspace: per-workgroup partials, per-point retry sums, counters, retry list.
 struct SweepLayout {
@@ -164,7 +177,7 @@ SweepLayout sweep_layout(uint32_t m, uint32_t n_points, uint64_t rpp)
     l.retry_off = (size_t)n_points * l.wpp * nv * 8;
     l.counts_off = l.retry_off + (size_t)n_points * nv * 8;
     l.list_off = l.counts_off + 256;
-    l.total = (l.list_off + (size_t)l.err_cap * 4 + 255) / 256 * 256;
+    l.total = align256(l.list_off + (size_t)l.err_cap * 4);
     return l;
 }
 constexpr double PIPE_MAX_RHO = 0.08;           // above this the per-lane kernel is cheaper
@@ -180,7 +193,7 @@ uint32_t max_slice_runs()
     const char *e = getenv("MSIM_MAX_SLICE_RUNS");
     const long long v = e ? atoll(e) : 0;
     if (v <= 0) return 0;
-    return v >= (1ll << 22) ? 1u << 22 : (uint32_t)((v + 255) / 256 * 256);
+    return v >= (1ll << 22) ? 1u << 22 : (uint32_t)align256((size_t)v);
 }
 
 // K1 wave slots of the current device (CUs x resident K1 waves per CU); 8192 if it cannot be queried.
@@ -214,75 +227,31 @@ msim::PipeLayout pipe_layout(const msim_config *c, uint64_t n_runs)
 int device_tables(msim_config *c, uint32_t seg, uint32_t nseg, msim::PipeTables *out)
 {
     using namespace msim;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return MSIM_E_HIP;
-    std::lock_guard<std::mutex> g(c->mu);
-    const size_t pick_b = sizeof(PickTab), log_b = sizeof(LogTab);
-    void *d = nullptr;
-    for (const auto &t : c->tables)
-        if (t.dev == dev && t.seg == seg && t.nseg >= nseg) d = t.ptr;
-    if (!d) {
-        const size_t jump_b = (size_t)nseg * 128 * 16;
-        std::vector<char> h(pick_b + log_b + jump_b);
-        build_pick_table(c->perc, c->prop, c->self, (int)c->n, (PickTab *)h.data());
-        build_log_table((LogTab *)(h.data() + pick_b));
-        build_jump_table(nseg, seg, (uint32_t *)(h.data() + pick_b + log_b));
-        if (hipMalloc(&d, h.size()) != hipSuccess) return MSIM_E_HIP;
-        if (hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return MSIM_E_HIP;
-        }
-        c->tables.push_back({dev, seg, nseg, d});
-    }
-    const char *b = (const char *)d;
+    const size_t pick_b = sizeof(PickTab), log_b = sizeof(LogTab), jump_b = (size_t)nseg * 128 * 16;
+    // an entry with the same segment length and at least as many segments serves: its jump table is a prefix
+    const char *b = (const char *)c->tables.get(
+        TAB_PIPE + seg, nseg, [&](uint64_t have) { return have >= nseg; }, pick_b + log_b + jump_b,
+        [&](char *h, const char *) {
+            build_pick_table(c->perc, c->prop, c->self, (int)c->n, (PickTab *)h);
+            build_log_table((LogTab *)(h + pick_b));
+            build_jump_table(nseg, seg, (uint32_t *)(h + pick_b + log_b));
+        });
+    if (!b) return MSIM_E_HIP;
     out->pick = (const PickTab *)b;
     out->logt = (const LogTab *)(b + pick_b);
     out->jump = (const uint32_t *)(b + pick_b + log_b);
     return MSIM_OK;
 }
 
-// Stage timing (msim_timing_enable / msim_timing_read): HIP events recorded on the launch stream.
-struct Timing {
-    std::mutex mu;
-    bool on = false;
-    std::vector<hipEvent_t> k1;      // (begin, end) pairs around K1
-    std::vector<hipEvent_t> launch;  // (begin, end) pairs around msim_launch
-    std::vector<hipEvent_t> engine;  // (begin, end) pairs around the entity engine (E1) of each slice
-    uint32_t launches = 0;
-};
-Timing &timing()
-{
-    static Timing t;
-    return t;
-}
-
-void destroy_events(std::vector<hipEvent_t> &v)
-{
-    for (auto e : v) (void)hipEventDestroy(e);
-    v.clear();
-}
-
-// Process-wide log table (msim_fastdraw.h) per device, for msim_device_intervals.
+// Process-wide log table (msim_fastdraw.h) per device, for msim_device_intervals and the entity engine. It
+// lives as long as the process: the cache is never destroyed.
 int global_log_table(const msim::LogTab **out)
 {
     static std::mutex mu;
-    static void *tab[MAX_DEVICES] = {nullptr};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return MSIM_E_HIP;
-    std::lock_guard<std::mutex> g(mu);
-    if (!tab[dev]) {
-        msim::LogTab h;
-        msim::build_log_table(&h);
-        void *d = nullptr;
-        if (hipMalloc(&d, sizeof(h)) != hipSuccess) return MSIM_E_HIP;
-        if (hipMemcpy(d, &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return MSIM_E_HIP;
-        }
-        tab[dev] = d;
-    }
-    *out = (const msim::LogTab *)tab[dev];
-    return MSIM_OK;
+    static TableCache *cache = new TableCache(mu);
+    *out = (const msim::LogTab *)cache->get(0, sizeof(msim::LogTab),
+                                            [](char *h, const char *) { msim::build_log_table((msim::LogTab *)h); });
+    return *out ? MSIM_OK : MSIM_E_HIP;
 }
 
 constexpr double WIDE_SLICE_BUDGET = 16.0 * (1ull << 30);
@@ -296,58 +265,35 @@ msim::WideLayout wide_layout(const msim_config *c, uint64_t n_runs)
 int wide_tables(msim_config *c, msim::WideArgs *a)
 {
     using namespace msim;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return MSIM_E_HIP;
     const uint32_t m = c->n;
     const WideGeom g = wide_geom(c->p.duration_ms);
     const size_t o_cf = 0, o_bkt = o_cf + 8 * ((size_t)m + 1), o_prop = (o_bkt + 2 * (size_t)WB_N + 7) / 8 * 8;
     const size_t o_log = o_prop + 8 * (size_t)m;
-    const size_t o_jm = (o_log + sizeof(LogTab) + 255) / 256 * 256, o_jt = o_jm + 64 * 2048,
-                 o_js = o_jt + 64 * 2048, total = o_js + 2048;
-    std::lock_guard<std::mutex> lk(c->mu);
-    void *d = nullptr;
-    for (const auto &t : c->wtables)
-        if (t.first == dev) d = t.second;
-    if (!d) {
-        std::vector<char> h(total, 0);
+    const size_t o_jm = align256(o_log + sizeof(LogTab)), o_jt = o_jm + 64 * 2048, o_js = o_jt + 64 * 2048,
+                 total = o_js + 2048;
+    const char *b = (const char *)c->tables.get(TAB_WIDE, total, [&](char *h, const char *) {
         std::vector<uint32_t> fthr(m);
         for (uint32_t k = 0; k < m; ++k) {
             fthr[k] = c->wprop[k] < (int64_t)FTHR_NEVER ? (uint32_t)c->wprop[k] : FTHR_NEVER;
-            ((int64_t *)(h.data() + o_prop))[k] = c->wprop[k];
+            ((int64_t *)(h + o_prop))[k] = c->wprop[k];
         }
-        build_wide_pick(c->wperc.data(), fthr.data(), m, (uint32_t)c->total_weight, (uint64_t *)(h.data() + o_cf),
-                        (uint16_t *)(h.data() + o_bkt));
-        build_log_table((LogTab *)(h.data() + o_log));
+        build_wide_pick(c->wperc.data(), fthr.data(), m, (uint32_t)c->total_weight, (uint64_t *)(h + o_cf),
+                        (uint16_t *)(h + o_bkt));
+        build_log_table((LogTab *)(h + o_log));
         // jmain[l] = T^(l*S0); jtail[l] = T^(B0 + l*ST); jstep = T^(63*ST - 1)
-        auto store = [](const Mat128 &mm, uint32_t *w) {
-            for (int col = 0; col < 128; ++col) {
-                w[4 * col + 0] = (uint32_t)mm.lo[col];
-                w[4 * col + 1] = (uint32_t)(mm.lo[col] >> 32);
-                w[4 * col + 2] = (uint32_t)mm.hi[col];
-                w[4 * col + 3] = (uint32_t)(mm.hi[col] >> 32);
-            }
-        };
-        build_jump_table(64, g.S0, (uint32_t *)(h.data() + o_jm));
-        {
-            Mat128 step, cur, tmp;
-            mat_pow(g.B0, cur);
-            mat_pow(g.ST, step);
-            for (uint32_t l = 0; l < 64; ++l) {
-                store(cur, (uint32_t *)(h.data() + o_jt) + (size_t)l * 512);
-                mat_mul(step, cur, tmp);
-                cur = tmp;
-            }
-            mat_pow(63ull * g.ST - 1, tmp);
-            store(tmp, (uint32_t *)(h.data() + o_js));
+        build_jump_table(64, g.S0, (uint32_t *)(h + o_jm));
+        Mat128 step, cur, tmp;
+        mat_pow(g.B0, cur);
+        mat_pow(g.ST, step);
+        for (uint32_t l = 0; l < 64; ++l) {
+            mat_store(cur, (uint32_t *)(h + o_jt) + (size_t)l * 512);
+            mat_mul(step, cur, tmp);
+            cur = tmp;
         }
-        if (hipMalloc(&d, total) != hipSuccess) return MSIM_E_HIP;
-        if (hipMemcpy(d, h.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return MSIM_E_HIP;
-        }
-        c->wtables.push_back({dev, d});
-    }
-    const char *b = (const char *)d;
+        mat_pow(63ull * g.ST - 1, tmp);
+        mat_store(tmp, (uint32_t *)(h + o_js));
+    });
+    if (!b) return MSIM_E_HIP;
     a->cf = (const uint64_t *)(b + o_cf);
     a->bucket = (const uint16_t *)(b + o_bkt);
     a->prop = (const int64_t *)(b + o_prop);
@@ -385,28 +331,27 @@ constexpr double GEN_BUDGET = 2048.0 * (1 << 20);
 
 SelWs sel_ws_layout(uint32_t m, uint32_t np, uint64_t rpp, int64_t duration_ms, uint32_t max_nr = 1u << 22)
 {
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     SelWs w;
     // one slice of every run (up to 2^22 runs per point: cold slots ~1.4 GiB; fewer under MSIM_MAX_SLICE_RUNS,
     // which thereby caps the segment-parallel form too: its records are laid out for this nr, sel_cfg_layout)
     if (const uint32_t cap = max_slice_runs()) max_nr = cap < max_nr ? cap : max_nr;
-    const uint64_t want = (rpp + 255) / 256 * 256;
+    const uint64_t want = align256(rpp);
     w.nr = (uint32_t)(want < max_nr ? want : max_nr);
     w.wpp = (uint32_t)((rpp + msim::TPB - 1) / msim::TPB);
     w.err_cap = (uint32_t)(rpp * np);  // every lane can be retried: the list never overflows
     const size_t nv = 6 * (size_t)m;
     w.counts_off = 0;
     w.partials_off = 256;
-    w.retry_off = al(w.partials_off + (size_t)np * w.wpp * nv * 8);
-    w.list_off = al(w.retry_off + (size_t)np * nv * 8);
+    w.retry_off = align256(w.partials_off + (size_t)np * w.wpp * nv * 8);
+    w.list_off = align256(w.retry_off + (size_t)np * nv * 8);
     // cold slots: one set per E1 lane of a slice (every point x the slice's runs, rounded to whole
     // workgroups) and per E2 lane
     const size_t e1 = (size_t)np * ((w.nr + msim::TPB - 1) / msim::TPB) * msim::TPB;
     w.cold_lanes = e1 > w.err_cap ? e1 : (size_t)w.err_cap;
-    w.cold_off = al(w.list_off + (size_t)w.err_cap * 4);
-    w.gen_off = al(w.cold_off + w.cold_lanes * msim::SEL_NC * sizeof(msim::ColdAct));
+    w.cold_off = align256(w.list_off + (size_t)w.err_cap * 4);
+    w.gen_off = align256(w.cold_off + w.cold_lanes * msim::SEL_NC * sizeof(msim::ColdAct));
     w.g = msim::gen_ws_layout(m, duration_ms, w.err_cap, GEN_FALLBACK_BUDGET, true);
-    w.total = al(w.gen_off + w.g.total);
+    w.total = align256(w.gen_off + w.g.total);
     return w;
 }
 
@@ -425,7 +370,6 @@ struct SegLayout {
 };
 SegLayout seg_layout_nr(uint32_t m, double rate, int64_t duration_ms, uint32_t nr)
 {
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     SegLayout L;
     L.nr = nr;
     const double mu = (double)duration_ms / 599999.5, sd = sqrt(mu > 1.0 ? mu : 1.0);
@@ -451,16 +395,16 @@ SegLayout seg_layout_nr(uint32_t m, double rate, int64_t duration_ms, uint32_t n
     L.cap = (uint32_t)ceil(lam + 6.0 * sqrt(lam) + 16.0);
     L.qcap = msim::seg_qcap((uint32_t)ceil(lam), L.seg);
     L.recs_off = 0;
-    L.cnt_off = al((size_t)nr * L.nseg * L.cap * msim::seg_rec_bytes(m));
-    L.qrecs_off = al(L.cnt_off + (size_t)L.nseg * nr * 4);
-    L.qcnt_off = al(L.qrecs_off + (size_t)nr * L.nseg * L.qcap * msim::seg_qrec_bytes(m));
-    L.total = al(L.qcnt_off + (size_t)L.nseg * nr * 4);
+    L.cnt_off = align256((size_t)nr * L.nseg * L.cap * msim::seg_rec_bytes(m));
+    L.qrecs_off = align256(L.cnt_off + (size_t)L.nseg * nr * 4);
+    L.qcnt_off = align256(L.qrecs_off + (size_t)nr * L.nseg * L.qcap * msim::seg_qrec_bytes(m));
+    L.total = align256(L.qcnt_off + (size_t)L.nseg * nr * 4);
     return L;
 }
 // Runs per slice of the segment-parallel form: the records of one slice within SEG_BUDGET.
 uint32_t seg_max_nr(uint32_t m, double rate, int64_t duration_ms, uint64_t n_runs)
 {
-    uint64_t nr = (n_runs + 255) / 256 * 256;
+    uint64_t nr = align256(n_runs);
     if (nr > (1u << 22)) nr = 1u << 22;
     for (;;) {  // the geometry depends on the slice size: shrink until one slice's records fit the budget
         const SegLayout L = seg_layout_nr(m, rate, duration_ms, (uint32_t)nr);
@@ -539,10 +483,23 @@ struct SelGroupDev {
     uint32_t uni;  // every point of the group has a uniform propagation delay
 };
 
-// The segment-parallel form's device arguments for one launch (msim_selseg.h).
-struct SegPlan {
-    msim::SegArgs g;
-};
+// G's arguments for the runs of one launch (the lists and tiers are launch_gen_tiers' business).
+msim::GenArgs gen_args(const msim::GenParams *d_gpts, uint32_t m, uint64_t run_begin, uint64_t rpp, uint32_t seed_base,
+                       uint64_t *sums, void *d_per_run, void *d_best_height, uint32_t *counts)
+{
+    msim::GenArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.pts = d_gpts;
+    ga.rpp = (uint32_t)rpp;
+    ga.max_m = m;
+    ga.run_begin = run_begin;
+    ga.seed_base = seed_base;
+    ga.sums = sums;
+    ga.records = (uint32_t *)d_per_run;
+    ga.best_h = (uint32_t *)d_best_height;
+    ga.counts = counts;
+    return ga;
+}
 
 // The slice loop of one launch: E1 per group (or SW + ST for a single network the segment-parallel form serves)
 // -> E2 (retries) -> G (what E2 cannot finish) -> F.
@@ -550,7 +507,7 @@ int sel_launch_impl(uint32_t m, uint32_t np, const msim::SelParams *d_pts, const
                     const std::vector<SelGroupDev> &groups, const msim::LogTab *logt, const SelWs &w, char *ws,
                     uint64_t run_begin, uint64_t rpp, uint32_t seed_base, void *d_sums, void *d_per_run,
                     void *d_best_height, void *d_status, hipStream_t s, std::vector<hipEvent_t> *engine_events,
-                    const SegPlan *seg = nullptr)
+                    const msim::SegArgs *seg = nullptr)
 {
     using namespace msim;
     uint32_t *counts = (uint32_t *)(ws + w.counts_off);
@@ -579,13 +536,12 @@ int sel_launch_impl(uint32_t m, uint32_t np, const msim::SelParams *d_pts, const
     a.cold_lanes = w.cold_lanes;
     a.gen_list = gen_first;
     a.force_gen = getenv("MSIM_SEL_FORCE_GEN") != nullptr ? 1u : 0u;
-    auto event = [&](std::vector<hipEvent_t> *v) -> hipEvent_t {
+    auto event = [&](std::vector<hipEvent_t> *v) {
         hipEvent_t e = nullptr;
         if (v && hipEventCreate(&e) == hipSuccess) {
             v->push_back(e);
             (void)hipEventRecord(e, s);
         }
-        return e;
     };
     uint32_t max_ns = 1;
     for (const auto &g : groups) max_ns = g.nscls > max_ns ? g.nscls : max_ns;
@@ -598,7 +554,7 @@ int sel_launch_impl(uint32_t m, uint32_t np, const msim::SelParams *d_pts, const
             a.plist = groups[0].plist;
             a.nlist = 1;
             a.uni = groups[0].uni;
-            if (launch_segwork(a, seg->g, m, s) != hipSuccess || launch_stitch(a, seg->g, m, s) != hipSuccess)
+            if (launch_segwork(a, *seg, m, s) != hipSuccess || launch_stitch(a, *seg, m, s) != hipSuccess)
                 return MSIM_E_HIP;
         }
         for (const auto &g : groups) {
@@ -613,17 +569,7 @@ int sel_launch_impl(uint32_t m, uint32_t np, const msim::SelParams *d_pts, const
     a.s0 = 0;
     a.sn = 0;
     if (launch_sel_retry(a, m, max_ns, s) != hipSuccess) return MSIM_E_HIP;
-    GenArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.pts = d_gpts;
-    ga.rpp = (uint32_t)rpp;
-    ga.max_m = m;
-    ga.run_begin = run_begin;
-    ga.seed_base = seed_base;
-    ga.sums = retry;
-    ga.records = (uint32_t *)d_per_run;
-    ga.best_h = (uint32_t *)d_best_height;
-    ga.counts = counts;
+    const GenArgs ga = gen_args(d_gpts, m, run_begin, rpp, seed_base, retry, d_per_run, d_best_height, counts);
     if (launch_gen_tiers(ga, w.g, gws, gen_first, counts + GEN_C_L1, 0, s) != hipSuccess) return MSIM_E_HIP;
     if (launch_sel_finalize(a.partials, np, w.wpp, 6 * m, retry, (uint64_t *)d_sums, counts, (uint32_t *)d_status, s) !=
         hipSuccess)
@@ -633,72 +579,46 @@ int sel_launch_impl(uint32_t m, uint32_t np, const msim::SelParams *d_pts, const
 
 // Device GenParams of a list of networks (one per point) and their weight / delay / selfish arrays, in one
 // allocation whose pointers are device addresses.
-int gen_tables_upload(const std::vector<const GenHost *> &hs, void **out)
+// The per-device copy is uploaded on first use (TAB_GEN of the config's or the sweep's cache).
+int gen_tables(TableCache &cache, const std::vector<const GenHost *> &hs, const msim::GenParams **out)
 {
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t np = hs.size();
-    size_t off = al(np * sizeof(msim::GenParams));
+    size_t off = align256(np * sizeof(msim::GenParams));
     std::vector<size_t> o(np);
     for (size_t i = 0; i < np; ++i) {
         o[i] = off;
-        off = al(off + hs[i]->w.size() * 21);
+        off = align256(off + hs[i]->w.size() * 21);
     }
-    std::vector<char> h(off, 0);
-    void *d = nullptr;
-    if (hipMalloc(&d, off) != hipSuccess) return MSIM_E_HIP;
-    for (size_t i = 0; i < np; ++i) {
-        const GenHost &g = *hs[i];
-        const size_t m = g.w.size();
-        uint64_t *cum = (uint64_t *)(h.data() + o[i]);
-        int64_t *prop = (int64_t *)(h.data() + o[i] + 8 * m);
-        uint32_t *cls = (uint32_t *)(h.data() + o[i] + 16 * m);
-        uint8_t *self = (uint8_t *)(h.data() + o[i] + 20 * m);
-        std::vector<uint32_t> cv;
-        uint32_t umax = msim::GEN_GENESIS;
-        gen_id_classes(g.ids, cv, &umax);
-        uint64_t c = 0;
-        for (size_t k = 0; k < m; ++k) {
-            cum[k] = (c += g.w[k]);
-            prop[k] = g.prop[k];
-            cls[k] = cv[k];
-            self[k] = g.self[k];
+    *out = (const msim::GenParams *)cache.get(TAB_GEN, off, [&](char *h, const char *d) {
+        for (size_t i = 0; i < np; ++i) {
+            const GenHost &g = *hs[i];
+            const size_t m = g.w.size();
+            uint64_t *cum = (uint64_t *)(h + o[i]);
+            int64_t *prop = (int64_t *)(h + o[i] + 8 * m);
+            uint32_t *cls = (uint32_t *)(h + o[i] + 16 * m);
+            uint8_t *self = (uint8_t *)(h + o[i] + 20 * m);
+            std::vector<uint32_t> cv;
+            uint32_t umax = msim::GEN_GENESIS;
+            gen_id_classes(g.ids, cv, &umax);
+            uint64_t c = 0;
+            for (size_t k = 0; k < m; ++k) {
+                cum[k] = (c += g.w[k]);
+                prop[k] = g.prop[k];
+                cls[k] = cv[k];
+                self[k] = g.self[k];
+            }
+            msim::GenParams *gp = (msim::GenParams *)h + i;
+            gp->duration_ms = g.duration_ms;
+            gp->mult = 0xFFFFFFFFFFFFFFFFull / g.W;
+            gp->m = (uint32_t)m;
+            gp->umax = umax;
+            gp->cum = (const uint64_t *)(d + o[i]);
+            gp->prop = (const int64_t *)(d + o[i] + 8 * m);
+            gp->cls = (const uint32_t *)(d + o[i] + 16 * m);
+            gp->self = (const uint8_t *)(d + o[i] + 20 * m);
         }
-        msim::GenParams *gp = (msim::GenParams *)h.data() + i;
-        gp->duration_ms = g.duration_ms;
-        gp->mult = 0xFFFFFFFFFFFFFFFFull / g.W;
-        gp->m = (uint32_t)m;
-        gp->umax = umax;
-        gp->cum = (const uint64_t *)((char *)d + o[i]);
-        gp->prop = (const int64_t *)((char *)d + o[i] + 8 * m);
-        gp->cls = (const uint32_t *)((char *)d + o[i] + 16 * m);
-        gp->self = (const uint8_t *)((char *)d + o[i] + 20 * m);
-    }
-    if (hipMemcpy(d, h.data(), off, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
-        return MSIM_E_HIP;
-    }
-    *out = d;
-    return MSIM_OK;
-}
-
-// The per-device copy of a table list (lazily uploaded, cached under `mu`).
-int gen_cached(std::mutex &mu, std::vector<std::pair<int, void *>> &cache, const std::vector<const GenHost *> &hs,
-               const msim::GenParams **out)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return MSIM_E_HIP;
-    std::lock_guard<std::mutex> g(mu);
-    for (const auto &t : cache)
-        if (t.first == dev) {
-            *out = (const msim::GenParams *)t.second;
-            return MSIM_OK;
-        }
-    void *d = nullptr;
-    const int rc = gen_tables_upload(hs, &d);
-    if (rc) return rc;
-    cache.push_back({dev, d});
-    *out = (const msim::GenParams *)d;
-    return MSIM_OK;
+    });
+    return *out ? MSIM_OK : MSIM_E_HIP;
 }
 
 // Workspace of a launch served by the general engine alone: counters, then G's lists and windows.
@@ -725,17 +645,7 @@ int gen_launch_impl(uint32_t m, uint32_t np, const msim::GenParams *d_gpts, cons
     if (hipMemsetAsync(counts, 0, GEN_C_WORDS * sizeof(uint32_t), s) != hipSuccess ||
         hipMemsetAsync(d_sums, 0, (size_t)np * 6 * m * 8, s) != hipSuccess)
         return MSIM_E_HIP;
-    GenArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.pts = d_gpts;
-    ga.rpp = (uint32_t)rpp;
-    ga.max_m = m;
-    ga.run_begin = run_begin;
-    ga.seed_base = seed_base;
-    ga.sums = (uint64_t *)d_sums;
-    ga.records = (uint32_t *)d_per_run;
-    ga.best_h = (uint32_t *)d_best_height;
-    ga.counts = counts;
+    const GenArgs ga = gen_args(d_gpts, m, run_begin, rpp, seed_base, (uint64_t *)d_sums, d_per_run, d_best_height, counts);
     if (launch_gen_tiers(ga, w.g, ws + w.gen_off, nullptr, nullptr, (uint32_t)(rpp * np), s) != hipSuccess ||
         launch_gen_status(counts, (uint32_t *)d_status, s) != hipSuccess)
         return MSIM_E_HIP;
@@ -745,25 +655,12 @@ int gen_launch_impl(uint32_t m, uint32_t np, const msim::GenParams *d_gpts, cons
 // Device copy of a config's SelParams and the point list {0}.
 int sel_config_tables(msim_config *c, const msim::SelParams **pts, const uint32_t **plist)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return MSIM_E_HIP;
-    std::lock_guard<std::mutex> g(c->mu);
-    void *d = nullptr;
-    for (const auto &t : c->stables)
-        if (t.first == dev) d = t.second;
-    const size_t pb = (sizeof(msim::SelParams) + 255) / 256 * 256;
-    if (!d) {
-        std::vector<char> h(pb + 256, 0);
-        memcpy(h.data(), &c->sp, sizeof(msim::SelParams));
-        if (hipMalloc(&d, h.size()) != hipSuccess) return MSIM_E_HIP;
-        if (hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return MSIM_E_HIP;
-        }
-        c->stables.push_back({dev, d});
-    }
+    const size_t pb = align256(sizeof(msim::SelParams));
+    const char *d = (const char *)c->tables.get(
+        TAB_SEL, pb + 256, [&](char *h, const char *) { memcpy(h, &c->sp, sizeof(msim::SelParams)); });
+    if (!d) return MSIM_E_HIP;
     *pts = (const msim::SelParams *)d;
-    *plist = (const uint32_t *)((const char *)d + pb);
+    *plist = (const uint32_t *)(d + pb);
     return MSIM_OK;
 }
 
@@ -934,6 +831,12 @@ int launch_wide_cfg(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs,
 
 }  // namespace
 
+void msim::config_weights(const msim_config *cfg, std::vector<uint64_t> *w, uint32_t *total_weight)
+{
+    *w = cfg->gh.w;  // every config keeps its miner list there, whichever engine serves it
+    *total_weight = (uint32_t)cfg->total_weight;
+}
+
 extern "C" {
 
 int msim_config_create(const msim_miner *miners, uint32_t n, int64_t duration_ms, msim_config **out)
@@ -959,23 +862,17 @@ int msim_config_set_concurrent_launches(msim_config *cfg, uint32_t n)
 
 void msim_config_destroy(msim_config *cfg)
 {
-    if (!cfg) return;
-    for (const auto &t : cfg->tables) (void)hipFree(t.ptr);
-    for (const auto &t : cfg->wtables) (void)hipFree(t.second);
-    for (const auto &t : cfg->stables) (void)hipFree(t.second);
-    for (const auto &t : cfg->gtables) (void)hipFree(t.second);
-    delete cfg;
+    delete cfg;  // its table cache frees the device tables
 }
 
 uint32_t msim_config_miner_count(const msim_config *cfg) { return cfg ? cfg->n : 0; }
 
 size_t msim_workspace_bytes(const msim_config *cfg, uint64_t n_runs)
 {
-    if (!cfg || n_runs == 0 || n_runs > MAX_LAUNCH_RUNS) return 0;
+    if (!cfg || n_runs == 0 || n_runs > msim::MAX_LAUNCH_RUNS) return 0;
     if (cfg->general) return gen_only_layout(cfg->n, 1, n_runs, cfg->p.duration_ms, cfg->gen_full).total;
     if (cfg->wide) return 256 + wide_layout(cfg, n_runs).total;
-    if (cfg->sel)
-        return sel_cfg_layout(cfg, n_runs).total;
+    if (cfg->sel) return sel_cfg_layout(cfg, n_runs).total;
     size_t t = ws_layout(cfg->n, n_runs).total;
     if (cfg->pipe_ok) t += pipe_layout(cfg, n_runs).total;
     return t;
@@ -985,114 +882,68 @@ int msim_launch(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uin
                 void *d_per_run, void *d_best_height, void *d_status, void *d_workspace, size_t workspace_bytes,
                 void *stream)
 {
-    if (!cfg || !d_sums || !d_status || !d_workspace || n_runs == 0 || n_runs > MAX_LAUNCH_RUNS) return MSIM_E_INVALID;
+    if (!cfg || !d_sums || !d_status || !d_workspace || n_runs == 0 || n_runs > msim::MAX_LAUNCH_RUNS) return MSIM_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    // Each branch brackets its launch with a LaunchTimer (msim_timing.h) once its tables are on the device.
     if (cfg->general) {
         const GenOnlyWs w = gen_only_layout(cfg->n, 1, n_runs, cfg->p.duration_ms, cfg->gen_full);
         if (workspace_bytes < w.total) return MSIM_E_INVALID;
         msim_config *c = const_cast<msim_config *>(cfg);
         const msim::GenParams *gp = nullptr;
-        int rc = gen_cached(c->mu, c->gtables, {&cfg->gh}, &gp);
+        const int rc = gen_tables(c->tables, {&cfg->gh}, &gp);
         if (rc) return rc;
-        Timing &tm = timing();
-        std::unique_lock<std::mutex> lk(tm.mu);
-        hipEvent_t lb = nullptr, le = nullptr;
-        hipStream_t s = (hipStream_t)stream;
-        if (tm.on) {
-            if (hipEventCreate(&lb) == hipSuccess && hipEventCreate(&le) == hipSuccess) {
-                tm.launch.push_back(lb);
-                tm.launch.push_back(le);
-                (void)hipEventRecord(lb, s);
-            }
-            tm.launches++;
-        } else {
-            lk.unlock();
-        }
-        rc = gen_launch_impl(cfg->n, 1, gp, w, (char *)d_workspace, run_begin, n_runs, seed_base, d_sums, d_per_run,
-                             d_best_height, d_status, s);
-        if (le) (void)hipEventRecord(le, s);
-        return rc;
+        msim::LaunchTimer timer(s);
+        return gen_launch_impl(cfg->n, 1, gp, w, (char *)d_workspace, run_begin, n_runs, seed_base, d_sums, d_per_run,
+                               d_best_height, d_status, s);
     }
     if (cfg->wide) {
-        Timing &tm = timing();
-        std::unique_lock<std::mutex> lk(tm.mu);
-        hipEvent_t lb = nullptr, le = nullptr;
-        std::vector<hipEvent_t> *w1 = nullptr;
-        if (tm.on) {
-            w1 = &tm.k1;
-            if (hipEventCreate(&lb) == hipSuccess && hipEventCreate(&le) == hipSuccess) {
-                tm.launch.push_back(lb);
-                tm.launch.push_back(le);
-                (void)hipEventRecord(lb, (hipStream_t)stream);
-            }
-            tm.launches++;
-        } else {
-            lk.unlock();
-        }
-        const int rc = launch_wide_cfg(cfg, run_begin, n_runs, seed_base, d_sums, d_per_run, d_best_height, d_status,
-                                       d_workspace, workspace_bytes, stream, w1);
-        if (le) (void)hipEventRecord(le, (hipStream_t)stream);
-        return rc;
+        msim::LaunchTimer timer(s);
+        return launch_wide_cfg(cfg, run_begin, n_runs, seed_base, d_sums, d_per_run, d_best_height, d_status,
+                               d_workspace, workspace_bytes, stream, timer.k1());
     }
     if (cfg->sel) {
         const SelCfgWs cw = sel_cfg_layout(cfg, n_runs);
         const SelWs &w = cw.w;
         if (workspace_bytes < cw.total) return MSIM_E_INVALID;
         msim_config *c = const_cast<msim_config *>(cfg);
-        SegPlan plan;
+        msim::SegArgs plan;
         if (cw.seg) {  // the segment-parallel form: jump matrices for offsets j * seg, records after E1's workspace
             msim::PipeTables tab;
             const int rt = device_tables(c, cw.L.seg, cw.L.nseg, &tab);
             if (rt) return rt;
-            plan.g.jump = tab.jump;
-            plan.g.recs = (char *)d_workspace + w.total + cw.L.recs_off;
-            plan.g.cnt = (uint32_t *)((char *)d_workspace + w.total + cw.L.cnt_off);
-            plan.g.qrecs = (char *)d_workspace + w.total + cw.L.qrecs_off;
-            plan.g.qcnt = (uint32_t *)((char *)d_workspace + w.total + cw.L.qcnt_off);
-            plan.g.nr = cw.L.nr;
-            plan.g.nseg = cw.L.nseg;
-            plan.g.seg = cw.L.seg;
-            plan.g.cap = cw.L.cap;
-            plan.g.qcap = cw.L.qcap;
-            plan.g.xth = 16;
-            if (const char *e = getenv("MSIM_SEG_XTH")) plan.g.xth = (uint32_t)atoi(e);
+            plan.jump = tab.jump;
+            plan.recs = (char *)d_workspace + w.total + cw.L.recs_off;
+            plan.cnt = (uint32_t *)((char *)d_workspace + w.total + cw.L.cnt_off);
+            plan.qrecs = (char *)d_workspace + w.total + cw.L.qrecs_off;
+            plan.qcnt = (uint32_t *)((char *)d_workspace + w.total + cw.L.qcnt_off);
+            plan.nr = cw.L.nr;
+            plan.nseg = cw.L.nseg;
+            plan.seg = cw.L.seg;
+            plan.cap = cw.L.cap;
+            plan.qcap = cw.L.qcap;
+            plan.xth = 16;
+            if (const char *e = getenv("MSIM_SEG_XTH")) plan.xth = (uint32_t)atoi(e);
         }
         const msim::SelParams *pts = nullptr;
         const uint32_t *plist = nullptr;
         int rc = sel_config_tables(c, &pts, &plist);
         if (rc) return rc;
         const msim::GenParams *gp = nullptr;
-        rc = gen_cached(c->mu, c->gtables, {&cfg->gh}, &gp);
+        rc = gen_tables(c->tables, {&cfg->gh}, &gp);
         if (rc) return rc;
         const msim::LogTab *lt = nullptr;
         rc = global_log_table(&lt);
         if (rc) return rc;
         std::vector<SelGroupDev> groups{{msim::sel_ns_class(cfg->sp.ns), 1u, plist, cfg->sp.uniform_prop != 0 ? 1u : 0u}};
-        Timing &tm = timing();
-        std::unique_lock<std::mutex> lk(tm.mu);
-        hipEvent_t lb = nullptr, le = nullptr;
-        hipStream_t s = (hipStream_t)stream;
-        const bool on = tm.on;
-        if (on) {
-            if (hipEventCreate(&lb) == hipSuccess && hipEventCreate(&le) == hipSuccess) {
-                tm.launch.push_back(lb);
-                tm.launch.push_back(le);
-                (void)hipEventRecord(lb, s);
-            }
-            tm.launches++;
-        } else {
-            lk.unlock();
-        }
-        rc = sel_launch_impl(cfg->n, 1, pts, gp, groups, lt, w, (char *)d_workspace, run_begin, n_runs, seed_base, d_sums,
-                             d_per_run, d_best_height, d_status, s, on ? &tm.engine : nullptr, cw.seg ? &plan : nullptr);
-        if (le) (void)hipEventRecord(le, s);
-        return rc;
+        msim::LaunchTimer timer(s);
+        return sel_launch_impl(cfg->n, 1, pts, gp, groups, lt, w, (char *)d_workspace, run_begin, n_runs, seed_base,
+                               d_sums, d_per_run, d_best_height, d_status, s, timer.engine(), cw.seg ? &plan : nullptr);
     }
     const WsLayout l = ws_layout(cfg->n, n_runs);
     msim::PipeLayout pl;
     if (cfg->pipe_ok) pl = pipe_layout(cfg, n_runs);
     if (workspace_bytes < l.total + (cfg->pipe_ok ? pl.total : 0)) return MSIM_E_INVALID;
     char *ws = (char *)d_workspace;
-    hipStream_t s = (hipStream_t)stream;
     uint32_t *counts = (uint32_t *)(ws + l.counts_off);
     if (hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), s) != hipSuccess) return MSIM_E_HIP;
     msim::LaunchArgs a;
@@ -1112,30 +963,15 @@ int msim_launch(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uin
     a.stream = s;
     a.pl = nullptr;
     a.pipe_ws = nullptr;
-    a.k1_events = nullptr;
     if (cfg->pipe_ok) {
         const int rc = device_tables(const_cast<msim_config *>(cfg), pl.seg, pl.nseg, &a.tab);
         if (rc) return rc;
         a.pl = &pl;
         a.pipe_ws = ws + l.total;
     }
-    Timing &tm = timing();
-    std::unique_lock<std::mutex> lk(tm.mu);
-    hipEvent_t lb = nullptr, le = nullptr;
-    if (tm.on) {
-        a.k1_events = &tm.k1;
-        if (hipEventCreate(&lb) == hipSuccess && hipEventCreate(&le) == hipSuccess) {
-            tm.launch.push_back(lb);
-            tm.launch.push_back(le);
-            (void)hipEventRecord(lb, s);
-        }
-        tm.launches++;
-    } else {
-        lk.unlock();
-    }
-    const int rc = msim::launch_runs(a) == hipSuccess ? MSIM_OK : MSIM_E_HIP;
-    if (le) (void)hipEventRecord(le, s);
-    return rc;
+    msim::LaunchTimer timer(s);
+    a.k1_events = timer.k1();
+    return msim::launch_runs(a) == hipSuccess ? MSIM_OK : MSIM_E_HIP;
 }
 
 int msim_device_log1p(const double *d_x, double *d_out, uint64_t n, void *stream)
@@ -1188,23 +1024,14 @@ void msim_sums_to_stats(const msim_sums *sums, uint32_t n, msim_stats *out)
     }
 }
 
-// Whether a workspace of `bytes` fits the current device's free memory (hipMemGetInfo).
-static bool workspace_fits(size_t bytes)
-{
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess) return true;  // let the allocation report it
-    return bytes <= fr;
-}
-
 int msim_run(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
              msim_stats *out_sums, msim_sums *opt_sums, msim_run_record *opt_per_run, uint32_t *opt_best_height)
 {
     if (!cfg || !out_sums || n_runs == 0) return MSIM_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
     const uint32_t m = cfg->n;
-    const uint64_t chunk = n_runs < MAX_LAUNCH_RUNS ? n_runs : MAX_LAUNCH_RUNS;
+    const uint64_t chunk = n_runs < msim::MAX_LAUNCH_RUNS ? n_runs : msim::MAX_LAUNCH_RUNS;
     const size_t wsb = msim_workspace_bytes(cfg, chunk);
-    void *ws = nullptr, *sums = nullptr, *status = nullptr, *rec = nullptr, *bh = nullptr;
     const bool want_rec = opt_per_run != nullptr;
     const bool want_bh = want_rec || opt_best_height != nullptr;
     int rc = MSIM_OK;
@@ -1213,26 +1040,25 @@ int msim_run(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32
     uint32_t *bh_out = opt_best_height ? opt_best_height : (want_rec ? bh_host.data() : nullptr);
     std::vector<uint64_t> acc(6 * (size_t)m, 0), part(6 * (size_t)m);
     uint32_t st[2];
-    hipStream_t s = nullptr;
     // G's last window can need tens of GB for one lane of a large network (msim_general_launch.h): a
     // workspace larger than the device's free memory is the network's size limit, not a HIP failure
-    if (cfg->general && !workspace_fits(wsb)) return MSIM_E_MINERS;
-    if (hipMalloc(&ws, wsb) != hipSuccess || hipMalloc(&sums, 6 * sizeof(uint64_t) * m) != hipSuccess ||
-        hipMalloc(&status, 2 * sizeof(uint32_t)) != hipSuccess ||
-        (want_rec && hipMalloc(&rec, chunk * m * sizeof(msim_run_record)) != hipSuccess) ||
-        (want_bh && hipMalloc(&bh, chunk * sizeof(uint32_t)) != hipSuccess) || hipStreamCreate(&s) != hipSuccess) {
-        rc = MSIM_E_HIP;
-        goto out;
-    }
+    if (cfg->general && !msim::workspace_fits(wsb)) return MSIM_E_MINERS;
+    msim::DevBuf ws, sums, status, rec, bh;
+    msim::DevStream stream;  // after the buffers: destroyed before they are freed
+    if (!ws.alloc(wsb) || !sums.alloc(6 * sizeof(uint64_t) * m) || !status.alloc(2 * sizeof(uint32_t)) ||
+        (want_rec && !rec.alloc(chunk * m * sizeof(msim_run_record))) || (want_bh && !bh.alloc(chunk * sizeof(uint32_t))) ||
+        !stream.create())
+        return MSIM_E_HIP;
+    hipStream_t s = stream.get();
     for (uint64_t off = 0; off < n_runs && rc == MSIM_OK; off += chunk) {
         const uint64_t cn = (n_runs - off) < chunk ? (n_runs - off) : chunk;
-        rc = msim_launch(cfg, run_begin + off, cn, seed_base, sums, rec, bh, status, ws, wsb, s);
+        rc = msim_launch(cfg, run_begin + off, cn, seed_base, sums.get(), rec.get(), bh.get(), status.get(), ws.get(), wsb, s);
         if (rc) break;
-        if (hipMemcpyAsync(part.data(), sums, part.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(st, status, sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            (want_rec && hipMemcpyAsync(opt_per_run + off * m, rec, cn * m * sizeof(msim_run_record),
+        if (hipMemcpyAsync(part.data(), sums.get(), part.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(st, status.get(), sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            (want_rec && hipMemcpyAsync(opt_per_run + off * m, rec.get(), cn * m * sizeof(msim_run_record),
                                         hipMemcpyDeviceToHost, s) != hipSuccess) ||
-            (want_bh && hipMemcpyAsync(bh_out + off, bh, cn * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            (want_bh && hipMemcpyAsync(bh_out + off, bh.get(), cn * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess) ||
             hipStreamSynchronize(s) != hipSuccess) {
             rc = MSIM_E_HIP;
             break;
@@ -1264,13 +1090,6 @@ int msim_run(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32
                 }
         }
     }
-out:
-    if (s) (void)hipStreamDestroy(s);
-    (void)hipFree(ws);
-    (void)hipFree(sums);
-    (void)hipFree(status);
-    (void)hipFree(rec);
-    (void)hipFree(bh);
     return rc;
 }
 
@@ -1346,11 +1165,7 @@ int msim_sweep_create(const msim_config *const *cfgs, uint32_t n_points, msim_sw
 
 void msim_sweep_destroy(msim_sweep *sw)
 {
-    if (!sw) return;
-    for (const auto &d : sw->dev) (void)hipFree(d.second);
-    for (const auto &d : sw->sdev) (void)hipFree(d.second);
-    for (const auto &d : sw->gdev) (void)hipFree(d.second);
-    delete sw;
+    delete sw;  // its table cache frees the device tables
 }
 
 uint32_t msim_sweep_point_count(const msim_sweep *sw) { return sw ? (uint32_t)sw->pts.size() : 0u; }
@@ -1358,7 +1173,7 @@ uint32_t msim_sweep_miner_count(const msim_sweep *sw) { return sw ? sw->m : 0u; 
 
 size_t msim_sweep_workspace_bytes(const msim_sweep *sw, uint64_t runs_per_point)
 {
-    if (!sw || runs_per_point == 0 || runs_per_point * sw->pts.size() > MAX_LAUNCH_RUNS) return 0;
+    if (!sw || runs_per_point == 0 || runs_per_point * sw->pts.size() > msim::MAX_LAUNCH_RUNS) return 0;
     if (sw->general) return gen_only_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point, sw->max_duration, sw->gen_full).total;
     if (sw->sel) return sel_ws_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point, sw->max_duration).total;
     return sweep_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point).total;
@@ -1370,13 +1185,14 @@ int msim_sweep_launch(const msim_sweep *sw, uint64_t run_begin, uint64_t runs_pe
 {
     if (!sw || !d_sums || !d_status || !d_workspace || runs_per_point == 0) return MSIM_E_INVALID;
     const uint32_t np = (uint32_t)sw->pts.size();
-    if (runs_per_point * np > MAX_LAUNCH_RUNS) return MSIM_E_INVALID;
+    if (runs_per_point * np > msim::MAX_LAUNCH_RUNS) return MSIM_E_INVALID;
+    // Stage timing brackets msim_launch only: a sweep launch takes no LaunchTimer and records nothing.
+    msim_sweep *sm = const_cast<msim_sweep *>(sw);  // its table cache fills on first use
     const msim::GenParams *gp = nullptr;
     if (sw->general || sw->sel) {
-        msim_sweep *sm = const_cast<msim_sweep *>(sw);
         std::vector<const GenHost *> hs;
         for (const auto &g : sm->gens) hs.push_back(&g);
-        const int rc = gen_cached(sm->mu, sm->gdev, hs, &gp);
+        const int rc = gen_tables(sm->tables, hs, &gp);
         if (rc) return rc;
         if (sw->general) {
             const GenOnlyWs w = gen_only_layout(sw->m, np, runs_per_point, sw->max_duration, sw->gen_full);
@@ -1388,31 +1204,16 @@ int msim_sweep_launch(const msim_sweep *sw, uint64_t run_begin, uint64_t runs_pe
     if (sw->sel) {
         const SelWs w = sel_ws_layout(sw->m, np, runs_per_point, sw->max_duration);
         if (workspace_bytes < w.total) return MSIM_E_INVALID;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return MSIM_E_HIP;
-        msim_sweep *sm = const_cast<msim_sweep *>(sw);
-        void *d = nullptr;
-        const size_t pb = (np * sizeof(msim::SelParams) + 255) / 256 * 256;
-        {
-            std::lock_guard<std::mutex> g(sm->mu);
-            for (const auto &x : sm->sdev)
-                if (x.first == dev) d = x.second;
-            if (!d) {
-                std::vector<char> h(pb + (size_t)np * 4, 0);
-                memcpy(h.data(), sm->sps.data(), np * sizeof(msim::SelParams));
-                uint32_t *pl = (uint32_t *)(h.data() + pb);
-                for (const auto &gr : sm->groups)
-                    for (uint32_t p : gr.points) *pl++ = p;
-                if (hipMalloc(&d, h.size()) != hipSuccess) return MSIM_E_HIP;
-                if (hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-                    (void)hipFree(d);
-                    return MSIM_E_HIP;
-                }
-                sm->sdev.push_back({dev, d});
-            }
-        }
+        const size_t pb = align256(np * sizeof(msim::SelParams));
+        const char *d = (const char *)sm->tables.get(TAB_SEL, pb + (size_t)np * 4, [&](char *h, const char *) {
+            memcpy(h, sm->sps.data(), np * sizeof(msim::SelParams));
+            uint32_t *pl = (uint32_t *)(h + pb);
+            for (const auto &gr : sm->groups)
+                for (uint32_t p : gr.points) *pl++ = p;
+        });
+        if (!d) return MSIM_E_HIP;
         std::vector<SelGroupDev> groups;
-        const uint32_t *pl = (const uint32_t *)((const char *)d + pb);
+        const uint32_t *pl = (const uint32_t *)(d + pb);
         for (const auto &gr : sm->groups) {
             uint32_t uni = 1;
             for (uint32_t p : gr.points) uni &= sm->sps[p].uniform_prop != 0 ? 1u : 0u;
@@ -1428,24 +1229,9 @@ int msim_sweep_launch(const msim_sweep *sw, uint64_t run_begin, uint64_t runs_pe
     }
     const SweepLayout l = sweep_layout(sw->m, np, runs_per_point);
     if (workspace_bytes < l.total) return MSIM_E_INVALID;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return MSIM_E_HIP;
-    void *pts = nullptr;
-    {
-        msim_sweep *w = const_cast<msim_sweep *>(sw);
-        std::lock_guard<std::mutex> g(w->mu);
-        for (const auto &d : w->dev)
-            if (d.first == dev) pts = d.second;
-        if (!pts) {
-            const size_t b = w->pts.size() * sizeof(msim::SimParams);
-            if (hipMalloc(&pts, b) != hipSuccess) return MSIM_E_HIP;
-            if (hipMemcpy(pts, w->pts.data(), b, hipMemcpyHostToDevice) != hipSuccess) {
-                (void)hipFree(pts);
-                return MSIM_E_HIP;
-            }
-            w->dev.push_back({dev, pts});
-        }
-    }
+    const size_t pts_b = np * sizeof(msim::SimParams);
+    const void *pts = sm->tables.get(TAB_POINTS, pts_b, [&](char *h, const char *) { memcpy(h, sm->pts.data(), pts_b); });
+    if (!pts) return MSIM_E_HIP;
     char *ws = (char *)d_workspace;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(ws + l.retry_off, 0, l.list_off - l.retry_off, s) != hipSuccess) return MSIM_E_HIP;
@@ -1479,148 +1265,29 @@ int msim_sweep_run(const msim_sweep *sw, uint64_t run_begin, uint64_t runs_per_p
     const size_t np = sw->pts.size(), m = sw->m, nr = np * runs_per_point;
     const size_t wsb = msim_sweep_workspace_bytes(sw, runs_per_point);
     if (!wsb) return MSIM_E_INVALID;
-    void *ws = nullptr, *sums = nullptr, *status = nullptr, *rec = nullptr, *bh = nullptr;
     std::vector<msim_sums> hs(np * m);
     uint32_t st[2] = {0, 0};
-    hipStream_t s = nullptr;
-    int rc = MSIM_OK;
-    if (sw->general && !workspace_fits(wsb)) return MSIM_E_MINERS;  // as in msim_run
-    if (hipMalloc(&ws, wsb) != hipSuccess || hipMalloc(&sums, hs.size() * sizeof(msim_sums)) != hipSuccess ||
-        hipMalloc(&status, sizeof(st)) != hipSuccess ||
-        (opt_per_run && hipMalloc(&rec, nr * m * sizeof(msim_run_record)) != hipSuccess) ||
-        (opt_best_height && hipMalloc(&bh, nr * sizeof(uint32_t)) != hipSuccess) || hipStreamCreate(&s) != hipSuccess) {
-        rc = MSIM_E_HIP;
-    } else {
-        rc = msim_sweep_launch(sw, run_begin, runs_per_point, seed_base, sums, rec, bh, status, ws, wsb, s);
-        if (rc == MSIM_OK &&
-            (hipMemcpyAsync(hs.data(), sums, hs.size() * sizeof(msim_sums), hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(st, status, sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
-             (opt_per_run && hipMemcpyAsync(opt_per_run, rec, nr * m * sizeof(msim_run_record), hipMemcpyDeviceToHost, s) != hipSuccess) ||
-             (opt_best_height && hipMemcpyAsync(opt_best_height, bh, nr * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess) ||
-             hipStreamSynchronize(s) != hipSuccess))
-            rc = MSIM_E_HIP;
-        if (rc == MSIM_OK && st[1] != 0) rc = MSIM_E_CAPACITY;
-    }
-    if (rc == MSIM_OK) {
-        if (opt_sums) memcpy(opt_sums, hs.data(), hs.size() * sizeof(msim_sums));
-        msim_sums_to_stats(hs.data(), (uint32_t)hs.size(), out_stats);
-    }
-    if (s) (void)hipStreamDestroy(s);
-    (void)hipFree(ws);
-    (void)hipFree(sums);
-    (void)hipFree(status);
-    (void)hipFree(rec);
-    (void)hipFree(bh);
-    return rc;
-}
-
-int msim_timing_enable(int on)
-{
-    Timing &tm = timing();
-    std::lock_guard<std::mutex> g(tm.mu);
-    destroy_events(tm.k1);
-    destroy_events(tm.launch);
-    destroy_events(tm.engine);
-    tm.launches = 0;
-    tm.on = on != 0;
+    if (sw->general && !msim::workspace_fits(wsb)) return MSIM_E_MINERS;  // as in msim_run
+    msim::DevBuf ws, sums, status, rec, bh;
+    msim::DevStream stream;  // after the buffers: destroyed before they are freed
+    if (!ws.alloc(wsb) || !sums.alloc(hs.size() * sizeof(msim_sums)) || !status.alloc(sizeof(st)) ||
+        (opt_per_run && !rec.alloc(nr * m * sizeof(msim_run_record))) ||
+        (opt_best_height && !bh.alloc(nr * sizeof(uint32_t))) || !stream.create())
+        return MSIM_E_HIP;
+    hipStream_t s = stream.get();
+    const int rc = msim_sweep_launch(sw, run_begin, runs_per_point, seed_base, sums.get(), rec.get(), bh.get(),
+                                     status.get(), ws.get(), wsb, s);
+    if (rc) return rc;
+    if (hipMemcpyAsync(hs.data(), sums.get(), hs.size() * sizeof(msim_sums), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(st, status.get(), sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        (opt_per_run && hipMemcpyAsync(opt_per_run, rec.get(), nr * m * sizeof(msim_run_record), hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        (opt_best_height && hipMemcpyAsync(opt_best_height, bh.get(), nr * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return MSIM_E_HIP;
+    if (st[1] != 0) return MSIM_E_CAPACITY;
+    if (opt_sums) memcpy(opt_sums, hs.data(), hs.size() * sizeof(msim_sums));
+    msim_sums_to_stats(hs.data(), (uint32_t)hs.size(), out_stats);
     return MSIM_OK;
-}
-
-int msim_timing_read_stages(double *draws_ms, double *engine_ms, double *launch_ms, uint32_t *launches)
-{
-    if (!draws_ms || !engine_ms || !launch_ms || !launches) return MSIM_E_INVALID;
-    Timing &tm = timing();
-    std::lock_guard<std::mutex> g(tm.mu);
-    double acc[3] = {0, 0, 0};
-    int rc = MSIM_OK;
-    std::vector<hipEvent_t> *vs[3] = {&tm.k1, &tm.engine, &tm.launch};
-    for (int pass = 0; pass < 3; ++pass) {
-        std::vector<hipEvent_t> &v = *vs[pass];
-        for (size_t i = 0; i + 1 < v.size(); i += 2) {
-            float ms = 0;
-            if (hipEventSynchronize(v[i + 1]) != hipSuccess || hipEventElapsedTime(&ms, v[i], v[i + 1]) != hipSuccess)
-                rc = MSIM_E_HIP;
-            acc[pass] += ms;
-        }
-    }
-    *draws_ms = acc[0];
-    *engine_ms = acc[1];
-    *launch_ms = acc[2];
-    *launches = tm.launches;
-    destroy_events(tm.k1);
-    destroy_events(tm.launch);
-    destroy_events(tm.engine);
-    tm.launches = 0;
-    return rc;
-}
-
-// Union length of (begin, end) event pairs. Events are timed against an anchor of their own device: a pair
-// whose begin cannot be timed against an existing anchor (hipEventElapsedTime fails across devices) starts a
-// new group with its begin as the anchor. Each group's intervals are sorted and merged; the result is the
-// largest group's busy time (one device's), so a timed run over several devices reads instead of failing.
-static int busy_ms(const std::vector<hipEvent_t> &v, double *out)
-{
-    *out = 0;
-    if (v.size() < 2) return MSIM_OK;
-    std::vector<hipEvent_t> anchors;
-    std::vector<std::vector<std::pair<double, double>>> groups;
-    for (size_t i = 0; i + 1 < v.size(); i += 2) {
-        if (hipEventSynchronize(v[i + 1]) != hipSuccess) return MSIM_E_HIP;
-        bool placed = false;
-        for (size_t g = 0; g < anchors.size() && !placed; ++g) {
-            float a = 0, b = 0;
-            if (hipEventElapsedTime(&a, anchors[g], v[i]) != hipSuccess) continue;
-            if (hipEventElapsedTime(&b, anchors[g], v[i + 1]) != hipSuccess) return MSIM_E_HIP;
-            groups[g].emplace_back(a, b);
-            placed = true;
-        }
-        if (!placed) {
-            float b = 0;
-            if (hipEventElapsedTime(&b, v[i], v[i + 1]) != hipSuccess) return MSIM_E_HIP;
-            anchors.push_back(v[i]);
-            groups.push_back({{0.0, (double)b}});
-        }
-    }
-    (void)hipGetLastError();  // the failed cross-device queries leave an error behind
-    for (auto &iv : groups) {
-        std::sort(iv.begin(), iv.end());
-        double lo = iv[0].first, hi = iv[0].second, acc = 0;
-        for (const auto &p : iv) {
-            if (p.first > hi) {
-                acc += hi - lo;
-                lo = p.first;
-                hi = p.second;
-            } else if (p.second > hi) {
-                hi = p.second;
-            }
-        }
-        acc += hi - lo;
-        *out = acc > *out ? acc : *out;
-    }
-    return MSIM_OK;
-}
-
-int msim_timing_read_all(msim_timing *out)
-{
-    if (!out) return MSIM_E_INVALID;
-    memset(out, 0, sizeof(*out));
-    int rc = MSIM_OK;
-    {
-        Timing &tm = timing();
-        std::lock_guard<std::mutex> g(tm.mu);
-        const std::vector<hipEvent_t> *vs[3] = {&tm.k1, &tm.engine, &tm.launch};
-        double *busy[3] = {&out->draws_busy_ms, &out->engine_busy_ms, &out->launch_busy_ms};
-        for (int i = 0; i < 3; ++i)
-            if (busy_ms(*vs[i], busy[i]) != MSIM_OK) rc = MSIM_E_HIP;
-    }
-    const int r2 = msim_timing_read_stages(&out->draws_ms, &out->engine_ms, &out->launch_ms, &out->launches);
-    return rc ? rc : r2;
-}
-
-int msim_timing_read(double *draws_ms, double *launch_ms, uint32_t *launches)
-{
-    double e = 0;
-    return msim_timing_read_stages(draws_ms, &e, launch_ms, launches);
 }
 
 int msim_pipeline_info(const msim_config *cfg, uint64_t n_runs, msim_pipeline_layout *out)
@@ -1674,92 +1341,6 @@ int msim_pipeline_info(const msim_config *cfg, uint64_t n_runs, msim_pipeline_la
     out->segments = pl.nseg;
     out->blocks_per_run = pl.nb;
     out->workspace_bytes = pl.total;
-    return MSIM_OK;
-}
-
-// ---------------------------------------------------------------- samplers (test.cpp)
-namespace {
-int sample_impl(int mode, const msim_config *cfg, uint64_t seed, uint64_t n, int device, unsigned long long *host_out,
-                size_t nout)
-{
-    using namespace msim;
-    if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-    const uint64_t target_threads = 131072;
-    uint64_t S64 = (n + target_threads - 1) / target_threads;
-    if (S64 < 64) S64 = 64;
-    if (S64 > 0xFFFFFFFFull) return MSIM_E_INVALID;
-    const uint32_t S = (uint32_t)S64;
-    // T^(S * 2^b), b = 0..31
-    std::vector<uint32_t> jumps(32 * 512);
-    {
-        Mat128 cur, tmp;
-        mat_pow(S, cur);
-        for (int b = 0; b < 32; ++b) {
-            uint32_t *w = jumps.data() + (size_t)b * 512;
-            for (int col = 0; col < 128; ++col) {
-                w[4 * col + 0] = (uint32_t)cur.lo[col];
-                w[4 * col + 1] = (uint32_t)(cur.lo[col] >> 32);
-                w[4 * col + 2] = (uint32_t)cur.hi[col];
-                w[4 * col + 3] = (uint32_t)(cur.hi[col] >> 32);
-            }
-            mat_mul(cur, cur, tmp);
-            cur = tmp;
-        }
-    }
-    uint32_t m = 0, W = 100;
-    std::vector<uint64_t> cf(1, 0xFFFFFFFFull);
-    std::vector<uint16_t> bucket(WB_N, 0);
-    if (mode == 0) {
-        m = cfg->n;
-        W = (uint32_t)cfg->total_weight;
-        std::vector<uint64_t> w(m);
-        for (uint32_t k = 0; k < m; ++k) w[k] = cfg->wide ? cfg->wperc[k] : cfg->perc[k];
-        std::vector<uint32_t> fthr(m, 0);
-        cf.assign(m + 1, 0);
-        build_wide_pick(w.data(), fthr.data(), m, W, cf.data(), bucket.data());
-    }
-    LogTab lt;
-    build_log_table(&lt);
-    const size_t bj = jumps.size() * 4, bc = cf.size() * 8, bb = bucket.size() * 2, bl = sizeof(lt), bo = nout * 8;
-    char *d = nullptr;
-    int rc = MSIM_OK;
-    hipStream_t st = nullptr;
-    if (hipMalloc((void **)&d, bj + bc + bb + bl + bo + 64) != hipSuccess || hipStreamCreate(&st) != hipSuccess) {
-        (void)hipFree(d);
-        return MSIM_E_HIP;
-    }
-    char *pj = d, *pc = pj + bj, *pb = pc + bc, *pl = pb + ((bb + 7) / 8 * 8), *po = pl + bl;
-    if (hipMemcpyAsync(pj, jumps.data(), bj, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(pc, cf.data(), bc, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(pb, bucket.data(), bb, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(pl, &lt, bl, hipMemcpyHostToDevice, st) != hipSuccess || hipMemsetAsync(po, 0, bo, st) != hipSuccess ||
-        launch_sample(mode, (const uint32_t *)pj, seed, n, S, (const uint64_t *)pc, (const uint16_t *)pb, m, W,
-                      0xFFFFFFFFFFFFFFFFull / W, (const LogTab *)pl, (unsigned long long *)po, st) != hipSuccess ||
-        hipMemcpyAsync(host_out, po, bo, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        rc = MSIM_E_HIP;
-    (void)hipStreamDestroy(st);
-    (void)hipFree(d);
-    return rc;
-}
-}  // namespace
-
-int msim_sample_picks(const msim_config *cfg, uint64_t seed, uint64_t n, uint64_t *out_counts, int device)
-{
-    if (!cfg || !out_counts) return MSIM_E_INVALID;
-    return sample_impl(0, cfg, seed, n, device, (unsigned long long *)out_counts, cfg->n + 1);
-}
-
-int msim_sample_intervals(uint64_t seed, uint64_t n, msim_interval_moments *out, int device)
-{
-    if (!out) return MSIM_E_INVALID;
-    unsigned long long o[4] = {0, 0, 0, 0};
-    const int rc = sample_impl(1, nullptr, seed, n, device, o, 4);
-    if (rc) return rc;
-    out->n = n;
-    out->sum = o[0];
-    out->sumsq_lo = o[1];
-    out->sumsq_hi = o[2];
-    out->max = o[3];
     return MSIM_OK;
 }
 

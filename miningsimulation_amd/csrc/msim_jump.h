@@ -93,20 +93,25 @@ inline void mat_pow(uint64_t n, Mat128 &out)
     out = acc;
 }
 
-// Host: matrices for draw offsets j*S, j = 0..nseg-1, packed as uint32 columns (4 words per column).
+// Host: one matrix as the kernels read it, packed as uint32 columns (4 words per column).
+inline void mat_store(const Mat128 &m, uint32_t *w /* 128*4 */)
+{
+    for (int c = 0; c < 128; ++c) {
+        w[4 * c + 0] = (uint32_t)m.lo[c];
+        w[4 * c + 1] = (uint32_t)(m.lo[c] >> 32);
+        w[4 * c + 2] = (uint32_t)m.hi[c];
+        w[4 * c + 3] = (uint32_t)(m.hi[c] >> 32);
+    }
+}
+
+// Host: matrices for draw offsets j*S, j = 0..nseg-1.
 inline void build_jump_table(uint32_t nseg, uint32_t seg, uint32_t *out /* nseg*128*4 */)
 {
     Mat128 step, cur, tmp;
     mat_pow(seg, step);
     mat_identity(cur);
     for (uint32_t j = 0; j < nseg; ++j) {
-        for (int c = 0; c < 128; ++c) {
-            uint32_t *w = out + ((size_t)j * 128 + c) * 4;
-            w[0] = (uint32_t)cur.lo[c];
-            w[1] = (uint32_t)(cur.lo[c] >> 32);
-            w[2] = (uint32_t)cur.hi[c];
-            w[3] = (uint32_t)(cur.hi[c] >> 32);
-        }
+        mat_store(cur, out + (size_t)j * 512);
         mat_mul(step, cur, tmp);
         cur = tmp;
     }

@@ -17,6 +17,7 @@
 
 #include <vector>
 
+#include "msim_host.h"
 #include "msim_moments.h"
 
 namespace msim {
@@ -155,7 +156,6 @@ void msim_moments_to_errors(const msim_moments *moments, uint32_t m, uint64_t n_
 // ---------------------------------------------------------------- host conveniences
 namespace {
 
-constexpr uint64_t MOM_MAX_LAUNCH_RUNS = 1ull << 26;  // msim_launch's per-call limit
 constexpr uint64_t MOM_CHUNK_BYTES = 1ull << 30;      // records of one chunk in device memory
 
 uint64_t chunk_cap()
@@ -179,7 +179,7 @@ int run_moments_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs,
     if (spec && (spec->bins == 0 || spec->bins > msim::MOM_MAX_BINS || spec->share_shift > 63 || spec->rate_shift > 63))
         return MSIM_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-    uint64_t chunk = MOM_MAX_LAUNCH_RUNS / np;
+    uint64_t chunk = msim::MAX_LAUNCH_RUNS / np;
     const uint64_t by_bytes = MOM_CHUNK_BYTES / ((uint64_t)np * m * sizeof(msim_run_record));
     if (chunk > by_bytes) chunk = by_bytes ? by_bytes : 1;
     if (const uint64_t cap = chunk_cap())
@@ -192,58 +192,38 @@ int run_moments_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs,
     const size_t n_hist = spec ? 2 * (size_t)(spec->bins + 2) * np * m : 0;
     std::vector<uint64_t> acc_s(n_sums, 0), part_s(n_sums), acc_m(n_mom, 0), part_m(n_mom), acc_h(n_hist, 0),
         part_h(n_hist);
-    void *ws = nullptr, *sums = nullptr, *status = nullptr, *rec = nullptr, *bh = nullptr, *mom = nullptr, *hist = nullptr;
-    hipStream_t s = nullptr;
     uint32_t st[2] = {0, 0};
-    int rc = MSIM_OK;
-    if (general) {  // as msim_run: a workspace beyond the device's free memory is the network's size limit
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess && wsb > fr) return MSIM_E_MINERS;
-    }
-    if (hipMalloc(&ws, wsb) != hipSuccess || hipMalloc(&sums, n_sums * sizeof(uint64_t)) != hipSuccess ||
-        hipMalloc(&status, sizeof(st)) != hipSuccess ||
-        hipMalloc(&rec, chunk * np * m * sizeof(msim_run_record)) != hipSuccess ||
-        hipMalloc(&bh, chunk * np * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&mom, n_mom * sizeof(uint64_t)) != hipSuccess ||
-        (n_hist && hipMalloc(&hist, n_hist * sizeof(uint64_t)) != hipSuccess) || hipStreamCreate(&s) != hipSuccess)
-        rc = MSIM_E_HIP;
-    for (uint64_t off = 0; off < runs && rc == MSIM_OK; off += chunk) {
+    // as msim_run: a workspace beyond the device's free memory is the network's size limit
+    if (general && !msim::workspace_fits(wsb)) return MSIM_E_MINERS;
+    msim::DevBuf ws, sums, status, rec, bh, mom, hist;
+    msim::DevStream stream;  // after the buffers: destroyed before they are freed
+    if (!ws.alloc(wsb) || !sums.alloc(n_sums * sizeof(uint64_t)) || !status.alloc(sizeof(st)) ||
+        !rec.alloc(chunk * np * m * sizeof(msim_run_record)) || !bh.alloc(chunk * np * sizeof(uint32_t)) ||
+        !mom.alloc(n_mom * sizeof(uint64_t)) || (n_hist && !hist.alloc(n_hist * sizeof(uint64_t))) || !stream.create())
+        return MSIM_E_HIP;
+    hipStream_t s = stream.get();
+    for (uint64_t off = 0; off < runs; off += chunk) {
         const uint64_t cn = runs - off < chunk ? runs - off : chunk;
-        rc = launch(run_begin + off, cn, sums, rec, bh, status, ws, wsb, s);
-        if (rc) break;
-        rc = msim_moments_launch(m, np, cn, rec, bh, spec, mom, hist, s);
-        if (rc) break;
-        if (hipMemcpyAsync(part_s.data(), sums, n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(st, status, sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(part_m.data(), mom, n_mom * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            (n_hist && hipMemcpyAsync(part_h.data(), hist, n_hist * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess) ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            rc = MSIM_E_HIP;
-            break;
-        }
-        if (st[1] != 0) {
-            rc = MSIM_E_CAPACITY;
-            break;
-        }
+        int rc = launch(run_begin + off, cn, sums.get(), rec.get(), bh.get(), status.get(), ws.get(), wsb, s);
+        if (rc) return rc;
+        rc = msim_moments_launch(m, np, cn, rec.get(), bh.get(), spec, mom.get(), hist.get(), s);
+        if (rc) return rc;
+        if (hipMemcpyAsync(part_s.data(), sums.get(), n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(st, status.get(), sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(part_m.data(), mom.get(), n_mom * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            (n_hist && hipMemcpyAsync(part_h.data(), hist.get(), n_hist * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return MSIM_E_HIP;
+        if (st[1] != 0) return MSIM_E_CAPACITY;
         for (size_t i = 0; i < n_sums; ++i) acc_s[i] += part_s[i];
         for (size_t i = 0; i < n_mom; ++i) acc_m[i] += part_m[i];
         for (size_t i = 0; i < n_hist; ++i) acc_h[i] += part_h[i];
     }
-    if (rc == MSIM_OK) {
-        if (opt_sums) memcpy(opt_sums, acc_s.data(), n_sums * sizeof(uint64_t));
-        msim_sums_to_stats((const msim_sums *)acc_s.data(), np * m, out_stats);
-        memcpy(out_moments, acc_m.data(), n_mom * sizeof(uint64_t));
-        if (n_hist) memcpy(opt_hist, acc_h.data(), n_hist * sizeof(uint64_t));
-    }
-    if (s) (void)hipStreamDestroy(s);
-    (void)hipFree(ws);
-    (void)hipFree(sums);
-    (void)hipFree(status);
-    (void)hipFree(rec);
-    (void)hipFree(bh);
-    (void)hipFree(mom);
-    (void)hipFree(hist);
-    return rc;
+    if (opt_sums) memcpy(opt_sums, acc_s.data(), n_sums * sizeof(uint64_t));
+    msim_sums_to_stats((const msim_sums *)acc_s.data(), np * m, out_stats);
+    memcpy(out_moments, acc_m.data(), n_mom * sizeof(uint64_t));
+    if (n_hist) memcpy(opt_hist, acc_h.data(), n_hist * sizeof(uint64_t));
+    return MSIM_OK;
 }
 
 }  // namespace

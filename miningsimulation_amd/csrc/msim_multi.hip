@@ -19,12 +19,13 @@
 
 #include "../../include/msim.h"
 #include "msim_commcache.h"
+#include "msim_host.h"
 
 namespace {
 
 // runs per msim_launch on one device (as msim_run: keeps every launch's workspace bounded)
 constexpr uint64_t MULTI_CHUNK = 1ull << 22;
-constexpr uint64_t MAX_LAUNCH_RUNS = 1ull << 26;  // msim_launch / msim_sweep_launch limit (runs x points)
+using msim::MAX_LAUNCH_RUNS;
 
 __global__ void add_sums_kernel(uint64_t *acc, const uint64_t *part, uint32_t n)
 {
@@ -40,16 +41,18 @@ __global__ void add_status_kernel(uint64_t *acc, const uint32_t *part)
 
 // One device's shard and everything it needs, allocated before any launch or collective.
 struct Shard {
-    int device;
-    uint64_t begin, n, chunk;
+    int device = 0;
+    uint64_t begin = 0, n = 0, chunk = 0;
     size_t wsb = 0;
     int rc = MSIM_OK;
-    hipStream_t s = nullptr;
-    void *ws = nullptr;
-    uint64_t *d_acc = nullptr;   // [nv + 2] sums of every chunk, then their status words (the all-reduce operand)
-    uint64_t *d_part = nullptr;  // [nv] one chunk's sums
-    uint32_t *d_pst = nullptr;   // [2] one chunk's status
+    msim::DevStream stream;
+    msim::DevBuf ws;
+    msim::DevBuf acc;   // [nv + 2] u64 sums of every chunk, then their status words (the all-reduce operand)
+    msim::DevBuf part;  // [nv] u64, one chunk's sums
+    msim::DevBuf pst;   // [2] u32, one chunk's status
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // timing: shard start, shard done, all-reduce done
+    hipStream_t s() const { return stream.get(); }
+    uint64_t *d_acc() const { return (uint64_t *)acc.get(); }
 };
 
 // What one device launches for a chunk of runs: a config (msim_launch) or a sweep (msim_sweep_launch).
@@ -83,11 +86,9 @@ int alloc_shard(const Job &job, Shard &sh, bool timed)
     sh.chunk = sh.n < mc ? sh.n : mc;
     sh.wsb = sh.chunk ? job.ws_bytes(sh.chunk) : 0;
     if (sh.chunk && sh.wsb == 0) return MSIM_E_INVALID;
-    if (hipSetDevice(sh.device) != hipSuccess || hipStreamCreate(&sh.s) != hipSuccess ||
-        hipMalloc(&sh.d_acc, (nv + 2) * sizeof(uint64_t)) != hipSuccess ||
-        hipMalloc(&sh.d_part, nv * sizeof(uint64_t)) != hipSuccess ||
-        hipMalloc(&sh.d_pst, 2 * sizeof(uint32_t)) != hipSuccess || (sh.wsb && hipMalloc(&sh.ws, sh.wsb) != hipSuccess) ||
-        hipMemsetAsync(sh.d_acc, 0, (nv + 2) * sizeof(uint64_t), sh.s) != hipSuccess)
+    if (hipSetDevice(sh.device) != hipSuccess || !sh.stream.create() || !sh.acc.alloc((nv + 2) * sizeof(uint64_t)) ||
+        !sh.part.alloc(nv * sizeof(uint64_t)) || !sh.pst.alloc(2 * sizeof(uint32_t)) ||
+        (sh.wsb && !sh.ws.alloc(sh.wsb)) || hipMemsetAsync(sh.d_acc(), 0, (nv + 2) * sizeof(uint64_t), sh.s()) != hipSuccess)
         return MSIM_E_HIP;
     if (timed)
         for (hipEvent_t &e : sh.ev)
@@ -97,14 +98,10 @@ int alloc_shard(const Job &job, Shard &sh, bool timed)
 
 void free_shard(Shard &sh)
 {
-    (void)hipSetDevice(sh.device);
-    (void)hipFree(sh.ws);
-    (void)hipFree(sh.d_part);
-    (void)hipFree(sh.d_pst);
-    (void)hipFree(sh.d_acc);
+    (void)hipSetDevice(sh.device);  // first: the buffers are freed and the stream destroyed on their own device
     for (hipEvent_t &e : sh.ev)
         if (e) (void)hipEventDestroy(e);
-    if (sh.s) (void)hipStreamDestroy(sh.s);
+    sh = Shard();  // what it held goes with the temporary: the buffers, then the stream
 }
 
 // Enqueue one device's shard (asynchronous: every device runs its chunks concurrently on its stream).
@@ -114,16 +111,17 @@ void enqueue_shard(const Job &job, uint32_t seed_base, Shard &sh)
         sh.rc = MSIM_E_HIP;
         return;
     }
-    if (sh.ev[0]) (void)hipEventRecord(sh.ev[0], sh.s);
+    if (sh.ev[0]) (void)hipEventRecord(sh.ev[0], sh.s());
     for (uint64_t off = 0; sh.rc == MSIM_OK && off < sh.n; off += sh.chunk) {
         const uint64_t cn = (sh.n - off) < sh.chunk ? (sh.n - off) : sh.chunk;
-        sh.rc = job.launch(sh.begin + off, cn, seed_base, sh.d_part, sh.d_pst, sh.ws, sh.wsb, sh.s);
+        sh.rc = job.launch(sh.begin + off, cn, seed_base, sh.part.get(), sh.pst.get(), sh.ws.get(), sh.wsb, sh.s());
         if (sh.rc) break;
-        hipLaunchKernelGGL(add_sums_kernel, dim3((job.nv + 255) / 256), dim3(256), 0, sh.s, sh.d_acc, sh.d_part, job.nv);
-        hipLaunchKernelGGL(add_status_kernel, dim3(1), dim3(64), 0, sh.s, sh.d_acc + job.nv, sh.d_pst);
+        hipLaunchKernelGGL(add_sums_kernel, dim3((job.nv + 255) / 256), dim3(256), 0, sh.s(), sh.d_acc(),
+                           (const uint64_t *)sh.part.get(), job.nv);
+        hipLaunchKernelGGL(add_status_kernel, dim3(1), dim3(64), 0, sh.s(), sh.d_acc() + job.nv, (const uint32_t *)sh.pst.get());
         if (hipGetLastError() != hipSuccess) sh.rc = MSIM_E_HIP;
     }
-    if (sh.ev[1]) (void)hipEventRecord(sh.ev[1], sh.s);
+    if (sh.ev[1]) (void)hipEventRecord(sh.ev[1], sh.s());
 }
 
 // Communicator cache (msim_commcache.h) over RCCL: one single-process communicator set per device list.
@@ -185,16 +183,16 @@ int run_job(const Job &job, uint64_t run_begin, uint64_t n_runs, uint32_t seed_b
             coll_failed = true;
         } else if (ce.ok) {
             for (uint32_t g = 0; g < n_devices; ++g)  // sums and status: one collective per device
-                if (ncclAllReduce(sh[g].d_acc, sh[g].d_acc, job.nv + 2, ncclUint64, ncclSum, ce.e->comms[g], sh[g].s) !=
+                if (ncclAllReduce(sh[g].d_acc(), sh[g].d_acc(), job.nv + 2, ncclUint64, ncclSum, ce.e->comms[g], sh[g].s()) !=
                     ncclSuccess)
                     rc = MSIM_E_HIP;
             if (ncclGroupEnd() != ncclSuccess) rc = MSIM_E_HIP;
             coll_failed = rc != MSIM_OK;
         }
         for (auto &x : sh)
-            if (x.ev[2]) (void)hipEventRecord(x.ev[2], x.s);
+            if (x.ev[2]) (void)hipEventRecord(x.ev[2], x.s());
         for (auto &x : sh)
-            if (hipSetDevice(x.device) != hipSuccess || hipStreamSynchronize(x.s) != hipSuccess) rc = rc ? rc : MSIM_E_HIP;
+            if (hipSetDevice(x.device) != hipSuccess || hipStreamSynchronize(x.s()) != hipSuccess) rc = rc ? rc : MSIM_E_HIP;
         for (const auto &x : sh)
             if (x.rc) rc = rc ? rc : x.rc;
         if (coll_failed) comm_cache().retire(ce);  // under the entry's lock (msim_commcache.h)
@@ -214,7 +212,7 @@ int run_job(const Job &job, uint64_t run_begin, uint64_t n_runs, uint32_t seed_b
     acc.assign(job.nv + 2, 0);
     if (rc == MSIM_OK) {  // every device holds the reduced sums and status: read the first one's
         if (hipSetDevice(sh[0].device) != hipSuccess ||
-            hipMemcpy(acc.data(), sh[0].d_acc, acc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+            hipMemcpy(acc.data(), sh[0].d_acc(), acc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
             rc = MSIM_E_HIP;
         else if (acc[job.nv + 1] != 0)
             rc = MSIM_E_CAPACITY;
