@@ -12,7 +12,7 @@
 //   msim_main [n_gpus] [seed_base] [default|c5]
 //   msim_main --grid H1,H2,..:P1,P2,.. [--runs R] [--gpus N] [--seed S] [--json]
 //        SetupMiners with miner 0 selfish at H% (miner 1 at 59-H%) and every propagation P ms
-//   msim_main --sweep FILE.json [--runs R] [--gpus N] [--seed S] [--json]
+//   msim_main --sweep FILE.json [--runs R] [--gpus N] [--seed S] [--json] [--contrast P]
 //        {"runs": R, "seed_base": S, "duration_ms": D, "total_weight": W,
 //         "grid": {"selfish_perc": [..], "propagation_ms": [..]}}            or
 //         "points": [{"miners": [{"id": 0, "perc": 40, "propagation_ms": 1000, "selfish": true}, ..]}, ..]}
@@ -21,6 +21,12 @@
 // (msim_run_moments / msim_sweep_run_moments, one GPU): " ± .." columns after each report line ("n/a" where a
 // standard error is undefined, i.e. for a single run) and an "errors" object per miner in --json output.
 // Without the flag the output is unchanged.
+//
+// --contrast P (sweeps; composes with --errors): every point against point P (from 0) on the same seeds, from the
+// exact on-device cross sums (msim_sweep_run_contrasts, one GPU). After each other point's report lines one line
+// per miner: its difference to the same miner of point P with the standard error of the per-run difference, the
+// correlation of the two sides and the ratio; in --json output a "contrast" object per miner (msim_contrast's
+// fields). P outside the points is a usage error.
 //
 // Build: make -C host
 // "c5" runs BASELINE configs[4] (2 pools + 1 024 small miners, integer weights summing to
@@ -108,6 +114,32 @@ static std::string PlusMinus(double se, double scale, const char *unit)
     return buf;
 }
 
+// A number as the report prints its means (fmt: a printf format for one double), "n/a" for NaN.
+static std::string Num(const char *fmt, double v, double scale = 1.0)
+{
+    if (std::isnan(v)) return "n/a";
+    char buf[64];
+    std::snprintf(buf, sizeof(buf), fmt, v * scale);
+    return buf;
+}
+
+// The contrast lines of one point against point `baseline`, one per miner (contrasts.contrast_line in the package).
+static void PrintContrasts(size_t point, size_t baseline, const msim_contrast *c, size_t m)
+{
+    for (size_t k = 0; k < m; ++k) {
+        const msim_contrast &x = c[k];
+        std::printf("  - Miner %zu of point %zu vs point %zu: found %s ± %s blocks (corr %s), ×%s ± %s;"
+                    " share %s ± %s of blocks (corr %s), ×%s ± %s; stale rate %s ± %s (corr %s)\n",
+                    k, point, baseline, Num("%+g", x.found_diff).c_str(), Num("%g", x.found_diff_se).c_str(),
+                    Num("%.3g", x.found_corr).c_str(), Num("%g", x.found_ratio).c_str(),
+                    Num("%g", x.found_ratio_se).c_str(), Num("%+g%%", x.share_diff, 100.0).c_str(),
+                    Num("%g%%", x.share_diff_se, 100.0).c_str(), Num("%.3g", x.share_corr).c_str(),
+                    Num("%g", x.share_ratio).c_str(), Num("%g", x.share_ratio_se).c_str(),
+                    Num("%+g%%", x.rate_diff, 100.0).c_str(), Num("%g%%", x.rate_diff_se, 100.0).c_str(),
+                    Num("%.3g", x.rate_corr).c_str());
+    }
+}
+
 // main.cpp:224-234 for one network; with `errors` (--errors) the standard errors of the three means follow each line.
 static void PrintReport(const std::vector<Miner> &miners, const std::vector<msim_stats> &stats_total, uint64_t runs,
                         uint64_t total_weight, long long days, const msim_errors *errors = nullptr)
@@ -142,7 +174,7 @@ static void PrintJsonNumber(const char *sep, const char *name, double v)
 }
 
 static void PrintJson(size_t point, const std::vector<Miner> &miners, const std::vector<msim_stats> &st, uint64_t runs,
-                      uint64_t total_weight, const msim_errors *errors = nullptr)
+                      uint64_t total_weight, const msim_errors *errors = nullptr, const msim_contrast *contrast = nullptr)
 {
     std::printf("{\"point\": %zu, \"runs\": %llu, \"total_weight\": %llu, \"miners\": [", point,
                 (unsigned long long)runs, (unsigned long long)total_weight);
@@ -163,6 +195,16 @@ static void PrintJson(size_t point, const std::vector<Miner> &miners, const std:
             PrintJsonNumber(", ", "rate_se", e.rate_se);
             PrintJsonNumber(", ", "pooled_rate", e.pooled_rate);
             PrintJsonNumber(", ", "pooled_rate_se", e.pooled_rate_se);
+            std::printf("}");
+        }
+        if (contrast) {
+            const double *v = &contrast[i].found_diff;
+            static const char *const names[16] = {
+                "found_diff", "found_diff_se", "found_corr", "found_ratio", "found_ratio_se", "stale_diff",
+                "stale_diff_se", "stale_corr", "share_diff", "share_diff_se", "share_corr", "share_ratio",
+                "share_ratio_se", "rate_diff", "rate_diff_se", "rate_corr"};
+            static_assert(sizeof(msim_contrast) == sizeof(double) * 16, "msim_contrast is 16 doubles");
+            for (int f = 0; f < 16; ++f) PrintJsonNumber(f ? ", " : ", \"contrast\": {", names[f], v[f]);
             std::printf("}");
         }
         std::printf("}");
@@ -213,6 +255,7 @@ struct SweepSpec {
     int gpus = 1;
     bool json = false;
     bool errors = false;
+    long long contrast = -1;  // --contrast P: the baseline point, or -1
 };
 
 static void AddGrid(SweepSpec &sp, const std::vector<int64_t> &hs, const std::vector<int64_t> &props)
@@ -272,7 +315,31 @@ static int RunSweep(const SweepSpec &sp)
     const uint32_t m = cfgs.empty() ? 0 : msim_config_miner_count(cfgs[0]);
     std::vector<msim_stats> st(sp.points.size() * m);
     std::vector<msim_errors> errs;
-    if (rc == MSIM_OK && sp.errors) {
+    std::vector<msim_contrast> con;  // [point != baseline, in order][miner]
+    if (rc == MSIM_OK && sp.contrast >= 0) {
+        std::vector<msim_pair> pairs;
+        for (uint32_t p = 0; p < sp.points.size(); ++p)
+            for (uint32_t k = 0; k < m && p != (uint32_t)sp.contrast; ++k) pairs.push_back({p, k, (uint32_t)sp.contrast, k});
+        std::vector<msim_moments> mo(st.size());
+        std::vector<msim_cross> cross(pairs.size());
+        if (!pairs.empty())
+            rc = WithStdoutOnStderr([&] {
+                return msim_sweep_run_contrasts(sw, 0, sp.runs, sp.seed_base, 0, pairs.data(), (uint32_t)pairs.size(),
+                                                st.data(), nullptr, mo.data(), cross.data());
+            });
+        else  // a single point has nothing to be compared with
+            rc = WithStdoutOnStderr([&] {
+                return msim_sweep_run_moments(sw, 0, sp.runs, sp.seed_base, 0, st.data(), nullptr, mo.data(), nullptr, nullptr);
+            });
+        if (rc == MSIM_OK) {
+            con.resize(pairs.size());
+            msim_cross_to_contrasts(mo.data(), m, pairs.data(), cross.data(), (uint32_t)pairs.size(), sp.runs, con.data());
+            if (sp.errors) {
+                errs.resize(st.size());
+                msim_moments_to_errors(mo.data(), (uint32_t)mo.size(), sp.runs, errs.data());
+            }
+        }
+    } else if (rc == MSIM_OK && sp.errors) {
         std::vector<msim_moments> mo(st.size());
         errs.resize(st.size());
         rc = WithStdoutOnStderr([&] {
@@ -289,11 +356,14 @@ static int RunSweep(const SweepSpec &sp)
         for (size_t p = 0; p < sp.points.size(); ++p) {
             const std::vector<msim_stats> ps(st.begin() + p * m, st.begin() + (p + 1) * m);
             const msim_errors *pe = sp.errors ? errs.data() + p * m : nullptr;
+            const msim_contrast *pc = nullptr;
+            if (sp.contrast >= 0 && p != (size_t)sp.contrast) pc = con.data() + (p - (p > (size_t)sp.contrast)) * m;
             if (sp.json) {
-                PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe);
+                PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe, pc);
             } else {
                 std::printf("Point %zu of %zu:\n", p + 1, sp.points.size());
                 PrintReport(sp.points[p], ps, sp.runs, sp.total_weight, days, pe);
+                if (pc) PrintContrasts(p, (size_t)sp.contrast, pc, m);
             }
         }
     }
@@ -333,9 +403,16 @@ int main(int argc, char **argv)
                 else if (a == "--runs" && i + 1 < argc) sp.runs = std::stoull(argv[++i]);
                 else if (a == "--gpus" && i + 1 < argc) sp.gpus = std::stoi(argv[++i]);
                 else if (a == "--seed" && i + 1 < argc) sp.seed_base = (uint32_t)std::stoul(argv[++i]);
+                else if (a == "--contrast" && i + 1 < argc) {
+                    sp.contrast = std::stoll(argv[++i]);
+                    if (sp.contrast < 0) throw std::runtime_error("--contrast P: P is a point, from 0");
+                }
                 else throw std::runtime_error("unknown option " + a);
             }
             sp.errors = errors;
+            if (sp.contrast >= (long long)sp.points.size())
+                throw std::runtime_error("--contrast " + std::to_string(sp.contrast) + ": there are " +
+                                         std::to_string(sp.points.size()) + " points");
         } catch (const std::exception &e) {
             std::fprintf(stderr, "msim_main: %s\n", e.what());
             return 2;

@@ -106,9 +106,10 @@ int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t du
  * A third, MSIM_PIPE_FORCE_RETRY (set to anything), read at every launch of the honest pipeline: its combine
  * kernel flags every run, so the retry kernel computes them all (what MSIM_SEL_FORCE_RETRY does on the entity
  * engine); at most 65 536 runs per launch then, the retry list's size.
- * A fourth, MSIM_MOMENTS_CHUNK_RUNS=<n> (n > 0), read only by msim_run_moments and msim_sweep_run_moments at every
- * call: a chunk of runs whose records stay in device memory holds at most n runs (per point), so a few hundred
- * runs exercise the chunk loop and its limb-by-limb addition. */
+ * A fourth, MSIM_MOMENTS_CHUNK_RUNS=<n> (n > 0), read only by msim_run_moments, msim_sweep_run_moments,
+ * msim_run_contrasts and msim_sweep_run_contrasts at every call: a chunk of runs whose records stay in device
+ * memory holds at most n runs (per point), so a few hundred runs exercise the chunk loop and its limb-by-limb
+ * addition. */
 int msim_config_is_wide(const msim_config *cfg);
 /* How many launches of this config the caller keeps in flight at once (default 1; e.g. 2 when steps
  * alternate over two HIP streams). The event-skipping pipeline plans its draw kernel's grid for it: three
@@ -299,8 +300,8 @@ int msim_moments_launch(uint32_t m, uint32_t n_points, uint64_t runs_per_point, 
  * only sums, status, moments and histograms come back; chunks of runs are added limb by limb on the host.
  * out_stats: from the fixed-point sums. out_moments: M (n_points * M) entries; opt_hist with opt_hist_spec:
  * M * 2 * (bins + 2) (times n_points) counts, or both NULL. MSIM_E_CAPACITY on a failed run, as msim_run.
- * A test switch, MSIM_MOMENTS_CHUNK_RUNS=<n> (n > 0), read only by these two functions: a chunk holds at most n
- * runs (per point), so a few hundred runs exercise the chunk loop. */
+ * A test switch, MSIM_MOMENTS_CHUNK_RUNS=<n> (n > 0), read only by these two functions and their contrast forms
+ * below: a chunk holds at most n runs (per point), so a few hundred runs exercise the chunk loop. */
 int msim_run_moments(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
                      msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments,
                      const msim_hist_spec *opt_hist_spec, uint64_t *opt_hist);
@@ -321,6 +322,73 @@ typedef struct msim_errors {
 } msim_errors;
 /* Host only. */
 void msim_moments_to_errors(const msim_moments *moments, uint32_t m, uint64_t n_runs, msim_errors *out);
+
+/* Paired contrasts: the difference, ratio and correlation of two (point, miner) columns of ONE launch's records,
+ * with standard errors. (No reference counterpart: the reference prints three means per miner of one network,
+ * main.cpp:224-234, and compares networks by rebuilding, README.md:21-27.) A sweep runs every point on the same
+ * seeds (above), so the two sides of a contrast between points share their draws and the per-run difference is far
+ * less noisy than either side; two miners of one network are negatively correlated, so there the independent
+ * formula understates the error. What msim_moments lacks for either is the cross term, summed here exactly.
+ * A pair names side a and side b; with f, s, share_t, rate_t of each side's record (and its own point's best
+ * height) as defined for msim_moments, msim_cross holds the sums over runs of f_a f_b, s_a s_b (64-bit products,
+ * two limbs), share_t,a share_t,b and rate_t,a rate_t,b (128-bit products, four limbs) in msim_moments' limb
+ * convention: limb i is the sum of the products' i-th 32-bit pieces, limbs are not normalised, exact up to
+ * 2^32 - 1 runs. Plain integer sums: identical for any split into workgroups, chunks, launches or ranks. A pair of
+ * a column with itself gives that column's four square sums of msim_moments. */
+typedef struct msim_pair {
+    uint32_t point_a, miner_a, point_b, miner_b;
+} msim_pair;
+typedef struct msim_cross {
+    uint64_t found_found[2]; /* sum f_a f_b */
+    uint64_t stale_stale[2]; /* sum s_a s_b */
+    uint64_t share_share[4]; /* sum share_t,a share_t,b */
+    uint64_t rate_rate[4];   /* sum rate_t,a rate_t,b */
+} msim_cross;
+#define MSIM_MAX_PAIRS 16776960u /* 65 535 tiles of 256 pairs: the grid of one msim_cross_launch */
+
+/* Device-resident and asynchronous on `stream`, as msim_moments_launch: no allocation, no synchronisation,
+ * independent of any config. d_per_run / d_best_height: as msim_moments_launch. d_pairs: n_pairs msim_pair in device
+ * memory. d_cross: n_pairs msim_cross, overwritten (zeroed inside the launch). A pair with a point >= n_points or a
+ * miner >= m reads nothing and leaves its twelve words zero (the launch cannot see device memory; validate on the
+ * host with msim_pairs_check). MSIM_E_INVALID, with nothing written, for m == 0, no points, no runs, more than
+ * 2^32 - 1 runs per point, n_pairs == 0 or above MSIM_MAX_PAIRS, or a null pointer. */
+int msim_cross_launch(uint32_t m, uint32_t n_points, uint64_t runs_per_point, const void *d_per_run,
+                      const void *d_best_height, const void *d_pairs, uint32_t n_pairs, void *d_cross, void *stream);
+/* Host only: MSIM_OK when there are 1..MSIM_MAX_PAIRS pairs and every one lies within n_points x m, else
+ * MSIM_E_INVALID. */
+int msim_pairs_check(uint32_t m, uint32_t n_points, const msim_pair *pairs, uint32_t n_pairs);
+/* msim_run_moments / msim_sweep_run_moments plus the cross sums of `pairs` (checked with msim_pairs_check, uploaded
+ * once; for a single config every pair has point_a == point_b == 0): every chunk adds msim_cross_launch on the same
+ * stream, and the chunks' cross words are added limb by limb on the host. out_cross: n_pairs entries. They follow
+ * MSIM_MOMENTS_CHUNK_RUNS as the two moments functions do. */
+int msim_run_contrasts(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                       const msim_pair *pairs, uint32_t n_pairs, msim_stats *out_stats, msim_sums *opt_sums,
+                       msim_moments *out_moments, msim_cross *out_cross);
+int msim_sweep_run_contrasts(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point,
+                             uint32_t seed_base, int device, const msim_pair *pairs, uint32_t n_pairs,
+                             msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments,
+                             msim_cross *out_cross);
+
+/* One pair's contrasts from N = n_runs runs. For each quantity, A and B are the sides' first sums, S_aa and S_bb
+ * their square sums (both from msim_moments), S_ab the cross sum:
+ *   diff     = (A - B) / N
+ *   diff_se  = sqrt((N (S_aa - 2 S_ab + S_bb) - (A - B)^2) / (N^2 (N - 1)))     the per-run difference's error
+ *   corr     = (N S_ab - A B) / sqrt((N S_aa - A^2) (N S_bb - B^2))             NaN when a variance is zero
+ *   ratio    = A / B (NaN for B == 0),  ratio_se = sqrt(N / (N - 1) (B^2 S_aa - 2 A B S_ab + A^2 S_bb)) / B^2
+ *              (found and share only; the delta method, as msim_errors' pooled_rate_se)
+ * share and rate differences are scaled by 2^-32. Every *_se and *_corr is NaN for N == 1. The integer numerators
+ * are formed exactly, signs handled explicitly, then a handful of correctly rounded f64 operations follow, so
+ * differently normalised limbs of one value give the same bits. */
+typedef struct msim_contrast {
+    double found_diff, found_diff_se, found_corr, found_ratio, found_ratio_se;
+    double stale_diff, stale_diff_se, stale_corr;
+    double share_diff, share_diff_se, share_corr, share_ratio, share_ratio_se;
+    double rate_diff, rate_diff_se, rate_corr;
+} msim_contrast;
+/* Host only. moments: n_points * m entries (of n_runs runs each), indexed point * m + miner by the pairs; pairs
+ * must pass msim_pairs_check for those counts. */
+void msim_cross_to_contrasts(const msim_moments *moments, uint32_t m, const msim_pair *pairs, const msim_cross *cross,
+                             uint32_t n_pairs, uint64_t n_runs, msim_contrast *out);
 
 /* Convert fixed-point sums to MinerStats-style doubles. */
 void msim_sums_to_stats(const msim_sums *sums, uint32_t n, msim_stats *out);

@@ -9,6 +9,7 @@ from .simulation import (  # noqa: F401
     C4_PROPAGATIONS_MS,
     C4_SELFISH_PERCS,
     C5_TOTAL_WEIGHT,
+    ContrastResult,
     PRESET_WEIGHTS,
     DEFAULT_SEED_BASE,
     PRESETS,
@@ -37,6 +38,17 @@ from .moments import (  # noqa: F401,E402
     errors_from_moments,
     hist_quantile,
     report_with_errors,
+)
+
+from .contrasts import (  # noqa: F401,E402
+    Pair,
+    contrasts,
+    contrasts_from_sums,
+    join_cross,
+    pairs_between_miners,
+    pairs_vs_baseline,
+    report_contrasts,
+    split_cross,
 )
 
 from . import model  # noqa: F401,E402  (first-order analytical stale-rate model, plot.py restated)

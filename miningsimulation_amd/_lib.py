@@ -62,6 +62,11 @@ EXPORTED = (
     "msim_run_moments",
     "msim_sweep_run_moments",
     "msim_moments_to_errors",
+    "msim_cross_launch",
+    "msim_pairs_check",
+    "msim_run_contrasts",
+    "msim_sweep_run_contrasts",
+    "msim_cross_to_contrasts",
 )
 
 
@@ -137,6 +142,25 @@ class MsimHistSpec(ctypes.Structure):
 class MsimErrors(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in ("found_mean", "found_se", "share_mean", "share_se", "rate_mean",
                                                "rate_se", "pooled_rate", "pooled_rate_se")]
+
+
+class MsimPair(ctypes.Structure):
+    """msim_pair: side a and side b of a contrast, each a (point, miner) column of one launch's records."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("point_a", "miner_a", "point_b", "miner_b")]
+
+
+class MsimCross(ctypes.Structure):
+    """msim_cross: 12 uint64 per pair, the sums over runs of the sides' products (limbs not normalised)."""
+    _fields_ = [("found_found", ctypes.c_uint64 * 2), ("stale_stale", ctypes.c_uint64 * 2),
+                ("share_share", ctypes.c_uint64 * 4), ("rate_rate", ctypes.c_uint64 * 4)]
+
+
+class MsimContrast(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in (
+        "found_diff", "found_diff_se", "found_corr", "found_ratio", "found_ratio_se",
+        "stale_diff", "stale_diff_se", "stale_corr",
+        "share_diff", "share_diff_se", "share_corr", "share_ratio", "share_ratio_se",
+        "rate_diff", "rate_diff_se", "rate_corr")]
 
 
 def _load() -> ctypes.CDLL:
@@ -229,6 +253,19 @@ def _load() -> ctypes.CDLL:
     lib.msim_sweep_run_moments.restype = ctypes.c_int
     lib.msim_moments_to_errors.argtypes = [ctypes.POINTER(MsimMoments), u32, u64, ctypes.POINTER(MsimErrors)]
     lib.msim_moments_to_errors.restype = None
+    lib.msim_cross_launch.argtypes = [u32, u32, u64, vp, vp, vp, u32, vp, vp]
+    lib.msim_cross_launch.restype = ctypes.c_int
+    lib.msim_pairs_check.argtypes = [u32, u32, ctypes.POINTER(MsimPair), u32]
+    lib.msim_pairs_check.restype = ctypes.c_int
+    lib.msim_run_contrasts.argtypes = [vp, u64, u64, u32, ctypes.c_int, ctypes.POINTER(MsimPair), u32,
+                                       ctypes.POINTER(MsimStats), ctypes.POINTER(MsimSums),
+                                       ctypes.POINTER(MsimMoments), ctypes.POINTER(MsimCross)]
+    lib.msim_run_contrasts.restype = ctypes.c_int
+    lib.msim_sweep_run_contrasts.argtypes = lib.msim_run_contrasts.argtypes
+    lib.msim_sweep_run_contrasts.restype = ctypes.c_int
+    lib.msim_cross_to_contrasts.argtypes = [ctypes.POINTER(MsimMoments), u32, ctypes.POINTER(MsimPair),
+                                            ctypes.POINTER(MsimCross), u32, u64, ctypes.POINTER(MsimContrast)]
+    lib.msim_cross_to_contrasts.restype = None
     lib.msim_version.argtypes = []
     lib.msim_version.restype = ctypes.c_char_p
     return lib

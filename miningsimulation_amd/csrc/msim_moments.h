@@ -119,27 +119,32 @@ inline void mom_accumulate_host(const msim_run_record *rec, const uint32_t *best
 }
 
 // ---------------------------------------------------------------- host: fixed-width unsigned integers
-// 384 bits: the widest numerator below, F^2 * sum(s^2) + S^2 * sum(f^2) with F, S < 2^64 and the square sums
-// < 2^97, stays under 2^226; N * (that) under 2^258.
-struct MomWide {
-    static constexpr int W = 12;  // 32-bit limbs
+// MomWide, 384 bits: the widest numerator below, F^2 * sum(s^2) + S^2 * sum(f^2) with F, S < 2^64 and the square
+// sums < 2^97, stays under 2^226; N * (that) under 2^258. The helpers take any limb count (msim_cross.h needs
+// more); results are exact integers, so they do not depend on it.
+template <int LIMBS>
+struct WideU {
+    static constexpr int W = LIMBS;  // 32-bit limbs
     uint32_t w[W];
 };
+using MomWide = WideU<12>;
 
-inline MomWide mw_from_u64(uint64_t x)
+template <int W = MomWide::W>
+inline WideU<W> mw_from_u64(uint64_t x)
 {
-    MomWide r;
+    WideU<W> r;
     memset(&r, 0, sizeof(r));
     r.w[0] = (uint32_t)x;
     r.w[1] = (uint32_t)(x >> 32);
     return r;
 }
 
-inline MomWide mw_add(const MomWide &a, const MomWide &b)
+template <int W>
+inline WideU<W> mw_add(const WideU<W> &a, const WideU<W> &b)
 {
-    MomWide r;
+    WideU<W> r;
     uint64_t c = 0;
-    for (int i = 0; i < MomWide::W; ++i) {
+    for (int i = 0; i < W; ++i) {
         c += (uint64_t)a.w[i] + b.w[i];
         r.w[i] = (uint32_t)c;
         c >>= 32;
@@ -148,11 +153,12 @@ inline MomWide mw_add(const MomWide &a, const MomWide &b)
 }
 
 // a - b for a >= b
-inline MomWide mw_sub(const MomWide &a, const MomWide &b)
+template <int W>
+inline WideU<W> mw_sub(const WideU<W> &a, const WideU<W> &b)
 {
-    MomWide r;
+    WideU<W> r;
     uint64_t borrow = 0;
-    for (int i = 0; i < MomWide::W; ++i) {
+    for (int i = 0; i < W; ++i) {
         const uint64_t d = (uint64_t)a.w[i] - b.w[i] - borrow;
         r.w[i] = (uint32_t)d;
         borrow = (d >> 32) & 1u;
@@ -160,22 +166,24 @@ inline MomWide mw_sub(const MomWide &a, const MomWide &b)
     return r;
 }
 
-inline int mw_cmp(const MomWide &a, const MomWide &b)
+template <int W>
+inline int mw_cmp(const WideU<W> &a, const WideU<W> &b)
 {
-    for (int i = MomWide::W - 1; i >= 0; --i)
+    for (int i = W - 1; i >= 0; --i)
         if (a.w[i] != b.w[i]) return a.w[i] < b.w[i] ? -1 : 1;
     return 0;
 }
 
-// a * b, truncated to 384 bits (no product below comes near)
-inline MomWide mw_mul(const MomWide &a, const MomWide &b)
+// a * b, truncated to the type's width (no product below comes near)
+template <int W>
+inline WideU<W> mw_mul(const WideU<W> &a, const WideU<W> &b)
 {
-    MomWide r;
+    WideU<W> r;
     memset(&r, 0, sizeof(r));
-    for (int i = 0; i < MomWide::W; ++i) {
+    for (int i = 0; i < W; ++i) {
         if (a.w[i] == 0) continue;
         uint64_t c = 0;
-        for (int j = 0; i + j < MomWide::W; ++j) {
+        for (int j = 0; i + j < W; ++j) {
             c += (uint64_t)a.w[i] * b.w[j] + r.w[i + j];
             r.w[i + j] = (uint32_t)c;
             c >>= 32;
@@ -185,14 +193,15 @@ inline MomWide mw_mul(const MomWide &a, const MomWide &b)
 }
 
 // sum(limb[i] << 32 i) of n unnormalised 64-bit limbs
-inline MomWide mw_join(const uint64_t *limb, int n)
+template <int W = MomWide::W>
+inline WideU<W> mw_join(const uint64_t *limb, int n)
 {
-    MomWide r;
+    WideU<W> r;
     memset(&r, 0, sizeof(r));
     for (int i = 0; i < n; ++i) {
         uint64_t c = (uint32_t)limb[i];
         uint64_t h = limb[i] >> 32;
-        for (int j = i; j < MomWide::W && (c || h); ++j) {
+        for (int j = i; j < W && (c || h); ++j) {
             c += r.w[j];
             r.w[j] = (uint32_t)c;
             c = (c >> 32) + h;
@@ -202,18 +211,20 @@ inline MomWide mw_join(const uint64_t *limb, int n)
     return r;
 }
 
-inline bool mw_is_zero(const MomWide &a)
+template <int W>
+inline bool mw_is_zero(const WideU<W> &a)
 {
-    for (int i = 0; i < MomWide::W; ++i)
+    for (int i = 0; i < W; ++i)
         if (a.w[i]) return false;
     return true;
 }
 
 // the nearest double (ties to even): the top 64 bits, with the bits below them folded into a sticky bit,
 // convert with one rounding; the scaling by a power of two is exact.
-inline double mw_to_double(const MomWide &a)
+template <int W>
+inline double mw_to_double(const WideU<W> &a)
 {
-    int top = MomWide::W - 1;
+    int top = W - 1;
     while (top >= 0 && a.w[top] == 0) --top;
     if (top < 0) return 0.0;
     if (top <= 1) return (double)(((uint64_t)(top == 1 ? a.w[1] : 0) << 32) | a.w[0]);

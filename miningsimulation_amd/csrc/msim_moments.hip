@@ -1,6 +1,7 @@
 // msim_moments.hip — second moments and histograms of the per-run terms, reduced on the device from the records
 // and best heights a launch writes on request (include/msim.h: msim_moments_launch, msim_run_moments,
-// msim_sweep_run_moments, msim_moments_to_errors). The arithmetic is msim_moments.h's.
+// msim_sweep_run_moments, msim_moments_to_errors; the host conveniences at the end also serve msim_run_contrasts
+// and msim_sweep_run_contrasts, whose kernel is msim_cross.hip's). The arithmetic is msim_moments.h's.
 //
 // Kernel layout. Grid = (run chunks, miner tiles, points), 256 threads. A tile holds `tm` consecutive miners
 // (at most 256), and thread t owns miner t % tm of the tile on rows t / tm, t / tm + 256 / tm, ... of its run
@@ -17,6 +18,7 @@
 
 #include <vector>
 
+#include "msim_cross.h"
 #include "msim_host.h"
 #include "msim_moments.h"
 
@@ -168,16 +170,25 @@ uint64_t chunk_cap()
 
 // Runs [run_begin, run_begin + runs) of n_points networks of m miners in chunks: launch(begin, cn, d_sums, d_rec,
 // d_bh, d_status, d_ws, wsb, stream) then msim_moments_launch on the same stream; only sums, status, moments
-// and histograms are copied back and added limb by limb.
+// and histograms are copied back and added limb by limb. With `cross` (msim_run_contrasts), its pairs are checked
+// and uploaded once, every chunk adds msim_cross_launch on the same stream, and the cross words come back and are
+// added the same way.
+struct CrossJob {
+    const msim_pair *pairs;
+    uint32_t n_pairs;
+    msim_cross *out;
+};
+
 template <class WsBytes, class Launch>
 int run_moments_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, int device, msim_stats *out_stats,
                      msim_sums *opt_sums, msim_moments *out_moments, const msim_hist_spec *spec, uint64_t *opt_hist,
-                     bool general, WsBytes ws_bytes, Launch launch)
+                     bool general, WsBytes ws_bytes, Launch launch, const CrossJob *cross)
 {
     if (!out_stats || !out_moments || runs == 0 || m == 0 || np == 0 || (spec != nullptr) != (opt_hist != nullptr))
         return MSIM_E_INVALID;
     if (spec && (spec->bins == 0 || spec->bins > msim::MOM_MAX_BINS || spec->share_shift > 63 || spec->rate_shift > 63))
         return MSIM_E_INVALID;
+    if (cross && (!cross->out || msim_pairs_check(m, np, cross->pairs, cross->n_pairs) != MSIM_OK)) return MSIM_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
     uint64_t chunk = msim::MAX_LAUNCH_RUNS / np;
     const uint64_t by_bytes = MOM_CHUNK_BYTES / ((uint64_t)np * m * sizeof(msim_run_record));
@@ -190,40 +201,82 @@ int run_moments_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs,
     if (!wsb) return MSIM_E_INVALID;
     const size_t n_sums = 6 * (size_t)np * m, n_mom = msim::MOM_WORDS * (size_t)np * m;
     const size_t n_hist = spec ? 2 * (size_t)(spec->bins + 2) * np * m : 0;
+    const size_t n_cross = cross ? msim::CROSS_WORDS * (size_t)cross->n_pairs : 0;
     std::vector<uint64_t> acc_s(n_sums, 0), part_s(n_sums), acc_m(n_mom, 0), part_m(n_mom), acc_h(n_hist, 0),
-        part_h(n_hist);
+        part_h(n_hist), acc_c(n_cross, 0), part_c(n_cross);
     uint32_t st[2] = {0, 0};
     // as msim_run: a workspace beyond the device's free memory is the network's size limit
     if (general && !msim::workspace_fits(wsb)) return MSIM_E_MINERS;
-    msim::DevBuf ws, sums, status, rec, bh, mom, hist;
+    msim::DevBuf ws, sums, status, rec, bh, mom, hist, pairs, crs;
     msim::DevStream stream;  // after the buffers: destroyed before they are freed
     if (!ws.alloc(wsb) || !sums.alloc(n_sums * sizeof(uint64_t)) || !status.alloc(sizeof(st)) ||
         !rec.alloc(chunk * np * m * sizeof(msim_run_record)) || !bh.alloc(chunk * np * sizeof(uint32_t)) ||
-        !mom.alloc(n_mom * sizeof(uint64_t)) || (n_hist && !hist.alloc(n_hist * sizeof(uint64_t))) || !stream.create())
+        !mom.alloc(n_mom * sizeof(uint64_t)) || (n_hist && !hist.alloc(n_hist * sizeof(uint64_t))) ||
+        (cross && (!pairs.alloc(cross->n_pairs * sizeof(msim_pair)) || !crs.alloc(n_cross * sizeof(uint64_t)))) ||
+        !stream.create())
         return MSIM_E_HIP;
     hipStream_t s = stream.get();
+    if (cross && hipMemcpy(pairs.get(), cross->pairs, cross->n_pairs * sizeof(msim_pair), hipMemcpyHostToDevice) != hipSuccess)
+        return MSIM_E_HIP;
     for (uint64_t off = 0; off < runs; off += chunk) {
         const uint64_t cn = runs - off < chunk ? runs - off : chunk;
         int rc = launch(run_begin + off, cn, sums.get(), rec.get(), bh.get(), status.get(), ws.get(), wsb, s);
         if (rc) return rc;
         rc = msim_moments_launch(m, np, cn, rec.get(), bh.get(), spec, mom.get(), hist.get(), s);
         if (rc) return rc;
+        if (cross) {
+            rc = msim_cross_launch(m, np, cn, rec.get(), bh.get(), pairs.get(), cross->n_pairs, crs.get(), s);
+            if (rc) return rc;
+        }
         if (hipMemcpyAsync(part_s.data(), sums.get(), n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipMemcpyAsync(st, status.get(), sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipMemcpyAsync(part_m.data(), mom.get(), n_mom * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
             (n_hist && hipMemcpyAsync(part_h.data(), hist.get(), n_hist * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            (n_cross && hipMemcpyAsync(part_c.data(), crs.get(), n_cross * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess) ||
             hipStreamSynchronize(s) != hipSuccess)
             return MSIM_E_HIP;
         if (st[1] != 0) return MSIM_E_CAPACITY;
         for (size_t i = 0; i < n_sums; ++i) acc_s[i] += part_s[i];
         for (size_t i = 0; i < n_mom; ++i) acc_m[i] += part_m[i];
         for (size_t i = 0; i < n_hist; ++i) acc_h[i] += part_h[i];
+        for (size_t i = 0; i < n_cross; ++i) acc_c[i] += part_c[i];
     }
     if (opt_sums) memcpy(opt_sums, acc_s.data(), n_sums * sizeof(uint64_t));
     msim_sums_to_stats((const msim_sums *)acc_s.data(), np * m, out_stats);
     memcpy(out_moments, acc_m.data(), n_mom * sizeof(uint64_t));
     if (n_hist) memcpy(opt_hist, acc_h.data(), n_hist * sizeof(uint64_t));
+    if (n_cross) memcpy(cross->out, acc_c.data(), n_cross * sizeof(uint64_t));
     return MSIM_OK;
+}
+
+int run_config(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+               msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments, const msim_hist_spec *spec,
+               uint64_t *opt_hist, const CrossJob *cross)
+{
+    if (!cfg) return MSIM_E_INVALID;
+    msim_pipeline_layout pl;
+    const bool general = msim_pipeline_info(cfg, 1, &pl) == MSIM_OK && pl.uses_pipeline == 4;
+    return run_moments_impl(
+        msim_config_miner_count(cfg), 1, run_begin, n_runs, device, out_stats, opt_sums, out_moments, spec, opt_hist,
+        general, [&](uint64_t n) { return msim_workspace_bytes(cfg, n); },
+        [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
+            return msim_launch(cfg, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
+        },
+        cross);
+}
+
+int run_sweep(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base, int device,
+              msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments, const msim_hist_spec *spec,
+              uint64_t *opt_hist, const CrossJob *cross)
+{
+    if (!sweep) return MSIM_E_INVALID;
+    return run_moments_impl(
+        msim_sweep_miner_count(sweep), msim_sweep_point_count(sweep), run_begin, runs_per_point, device, out_stats,
+        opt_sums, out_moments, spec, opt_hist, false, [&](uint64_t n) { return msim_sweep_workspace_bytes(sweep, n); },
+        [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
+            return msim_sweep_launch(sweep, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
+        },
+        cross);
 }
 
 }  // namespace
@@ -234,29 +287,35 @@ int msim_run_moments(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs
                      msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments,
                      const msim_hist_spec *opt_hist_spec, uint64_t *opt_hist)
 {
-    if (!cfg) return MSIM_E_INVALID;
-    msim_pipeline_layout pl;
-    const bool general = msim_pipeline_info(cfg, 1, &pl) == MSIM_OK && pl.uses_pipeline == 4;
-    return run_moments_impl(
-        msim_config_miner_count(cfg), 1, run_begin, n_runs, device, out_stats, opt_sums, out_moments, opt_hist_spec,
-        opt_hist, general, [&](uint64_t n) { return msim_workspace_bytes(cfg, n); },
-        [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
-            return msim_launch(cfg, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
-        });
+    return run_config(cfg, run_begin, n_runs, seed_base, device, out_stats, opt_sums, out_moments, opt_hist_spec,
+                      opt_hist, nullptr);
 }
 
 int msim_sweep_run_moments(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base,
                            int device, msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments,
                            const msim_hist_spec *opt_hist_spec, uint64_t *opt_hist)
 {
-    if (!sweep) return MSIM_E_INVALID;
-    return run_moments_impl(
-        msim_sweep_miner_count(sweep), msim_sweep_point_count(sweep), run_begin, runs_per_point, device, out_stats,
-        opt_sums, out_moments, opt_hist_spec, opt_hist, false,
-        [&](uint64_t n) { return msim_sweep_workspace_bytes(sweep, n); },
-        [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
-            return msim_sweep_launch(sweep, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
-        });
+    return run_sweep(sweep, run_begin, runs_per_point, seed_base, device, out_stats, opt_sums, out_moments,
+                     opt_hist_spec, opt_hist, nullptr);
+}
+
+int msim_run_contrasts(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                       const msim_pair *pairs, uint32_t n_pairs, msim_stats *out_stats, msim_sums *opt_sums,
+                       msim_moments *out_moments, msim_cross *out_cross)
+{
+    const CrossJob job = {pairs, n_pairs, out_cross};
+    return run_config(cfg, run_begin, n_runs, seed_base, device, out_stats, opt_sums, out_moments, nullptr, nullptr,
+                      &job);
+}
+
+int msim_sweep_run_contrasts(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point,
+                             uint32_t seed_base, int device, const msim_pair *pairs, uint32_t n_pairs,
+                             msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments,
+                             msim_cross *out_cross)
+{
+    const CrossJob job = {pairs, n_pairs, out_cross};
+    return run_sweep(sweep, run_begin, runs_per_point, seed_base, device, out_stats, opt_sums, out_moments, nullptr,
+                     nullptr, &job);
 }
 
 }  // extern "C"

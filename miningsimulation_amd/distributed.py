@@ -120,12 +120,40 @@ def run_sharded_moments(sim, n_total: int, seed_base: int, run_begin: int = 0, s
     Returns a SimulationResult (stats_total, sums, moments, hist, n_runs = n_total), identical on every rank.
     `launch` / `launch_moments` replace sim.launch / sim.launch_moments (same signatures, workspace None) so
     that the partition, chunking, packing and all-reduce can be exercised on CPU ranks with a gloo group."""
+    return _run_sharded_moments(sim, n_total, seed_base, run_begin, stream, launch, launch_moments, device, max_chunk,
+                                hist, None, None)[0]
+
+
+def run_sharded_contrasts(sim, n_total: int, seed_base: int, pairs, run_begin: int = 0, stream=None,
+                          launch: Optional[Callable] = None, launch_moments: Optional[Callable] = None,
+                          launch_cross: Optional[Callable] = None, device=None, max_chunk: int = MAX_LAUNCH_RUNS):
+    """run_sharded_moments plus the cross sums of `pairs` (contrasts.Pair, every one within point 0 of `sim`): every
+    chunk also runs msim_cross_launch on the launch stream, and the cross words are appended to the ONE int64
+    buffer of the ONE all-reduce. They are integer sums over runs too, so the result is bit-identical for every
+    world size and partition.
+
+    Returns a ContrastResult (points = [the SimulationResult of run_sharded_moments], pairs, cross), identical on
+    every rank. `launch_cross` replaces sim.launch_cross as `launch_moments` replaces sim.launch_moments."""
+    from .contrasts import Pair
+    from .simulation import ContrastResult
+
+    pairs = [Pair(*q) for q in pairs]
+    res, cross = _run_sharded_moments(sim, n_total, seed_base, run_begin, stream, launch, launch_moments, device,
+                                      max_chunk, None, pairs, launch_cross)
+    return ContrastResult(points=[res], pairs=pairs, cross=cross, n_runs=n_total)
+
+
+def _run_sharded_moments(sim, n_total, seed_base, run_begin, stream, launch, launch_moments, device, max_chunk, hist,
+                         pairs, launch_cross):
+    """(SimulationResult, cross sums or None): the body of run_sharded_moments, with the pairs' cross words behind
+    the histogram in the same buffer when `pairs` is given."""
     import contextlib
 
     import torch
     import torch.distributed as dist
 
     from ._lib import MsimSums
+    from .contrasts import CROSS_WORDS, cross_from_words, pairs_struct
     from .moments import MOMENT_WORDS, moments_from_words
     from .simulation import SimulationResult, sums_to_stats
 
@@ -136,7 +164,15 @@ def run_sharded_moments(sim, n_total: int, seed_base: int, run_begin: int = 0, s
     row = hist.bins + 2 if hist is not None else 0
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
     o_status, o_mom, o_hist = 6 * m, 6 * m + 2, 6 * m + 2 + MOMENT_WORDS * m
-    buf = torch.zeros(o_hist + 2 * row * m, dtype=torch.int64, device=dev)
+    o_cross = o_hist + 2 * row * m
+    n_pairs = len(pairs) if pairs is not None else 0
+    buf = torch.zeros(o_cross + CROSS_WORDS * n_pairs, dtype=torch.int64, device=dev)
+    if pairs is not None:
+        import numpy as np
+
+        pairs_struct(pairs, 1, m)  # ValueError for a pair outside the network
+        d_pairs = torch.from_numpy(np.asarray(pairs, dtype=np.uint32).reshape(-1, 4).view(np.int32)).to(dev)
+        pcross = torch.zeros((n_pairs, CROSS_WORDS), dtype=torch.int64, device=dev)
     part = torch.zeros((m, 6), dtype=torch.int64, device=dev)
     pst = torch.zeros(2, dtype=torch.int32, device=dev)
     pmom = torch.zeros((m, MOMENT_WORDS), dtype=torch.int64, device=dev)
@@ -161,7 +197,10 @@ def run_sharded_moments(sim, n_total: int, seed_base: int, run_begin: int = 0, s
             buf[o_status:o_mom] += pst
             buf[o_mom:o_hist] += pmom.view(-1)
             if hist is not None:
-                buf[o_hist:] += phist.view(-1)
+                buf[o_hist:o_cross] += phist.view(-1)
+            if pairs is not None:
+                (launch_cross or sim.launch_cross)(cn, rec, bh, d_pairs, n_pairs, pcross, stream=stream)
+                buf[o_cross:] += pcross.view(-1)
         if world > 1:
             dist.all_reduce(buf)
     if stream is not None and dev.type == "cuda":
@@ -171,10 +210,11 @@ def run_sharded_moments(sim, n_total: int, seed_base: int, run_begin: int = 0, s
         raise RuntimeError(f"{int(host[o_status + 1])} runs exceeded the compact state capacity")
     rows = host[:o_status].view(m, 6).tolist()
     u64 = (lambda v: int(v) & 0xFFFFFFFFFFFFFFFF)
+    cross = cross_from_words(host[o_cross:].view(n_pairs, CROSS_WORDS).numpy()) if pairs is not None else None
     return SimulationResult(
         stats_total=sums_to_stats([[u64(x) for x in r] for r in rows]),
         sums=[MsimSums(r[0], r[1], u64(r[2]), u64(r[3]), u64(r[4]), u64(r[5])) for r in rows],
         n_runs=n_total,
         moments=moments_from_words(host[o_mom:o_hist].view(m, MOMENT_WORDS).numpy()),
-        hist=host[o_hist:].view(m, 2, row).numpy().astype("uint64") if hist is not None else None,
-    )
+        hist=host[o_hist:o_cross].view(m, 2, row).numpy().astype("uint64") if hist is not None else None,
+    ), cross

@@ -20,7 +20,8 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import MsimMiner, MsimMoments, MsimRunRecord, MsimStats, MsimSums, MsimTiming, check, lib
+from ._lib import MsimCross, MsimMiner, MsimMoments, MsimRunRecord, MsimStats, MsimSums, MsimTiming, check, lib
+from .contrasts import CROSS_WORDS, Pair, cross_from_words, pairs_struct
 from .moments import MOMENT_WORDS, HistSpec, moments_from_words
 
 SIM_DURATION_MS = 31_556_952_000  # main.cpp:7 std::chrono::months{12}
@@ -109,6 +110,17 @@ class SimulationResult:
     hist: Optional[np.ndarray] = None           # [M, 2, bins + 2] uint64 counts (0 = share, 1 = rate), or None
 
 
+@dataclass
+class ContrastResult:
+    """What run_contrasts returns: the per-point results (moments filled) plus the pairs and their cross sums.
+    contrasts(result) turns them into differences, ratios and correlations with standard errors."""
+
+    points: List[SimulationResult]   # one per sweep point (one for a Simulation)
+    pairs: List[Pair]
+    cross: List[dict]                # per pair Python ints (contrasts.join_cross)
+    n_runs: int = 0
+
+
 def _launch_moments(m: int, n_points: int, runs_per_point: int, d_per_run, d_best_height, d_moments,
                     hist_spec: Optional[HistSpec], d_hist, stream) -> None:
     ptr = (lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None)
@@ -125,6 +137,33 @@ def _launch_moments(m: int, n_points: int, runs_per_point: int, d_per_run, d_bes
     spec = ctypes.byref(hist_spec.struct()) if hist_spec is not None else None
     check(lib.msim_moments_launch(m, n_points, runs_per_point, ptr(d_per_run), ptr(d_best_height), spec,
                                   ptr(d_moments), ptr(d_hist), sh), "msim_moments_launch")
+
+
+def _launch_cross(m: int, n_points: int, runs_per_point: int, d_per_run, d_best_height, d_pairs, n_pairs: int,
+                  d_cross, stream) -> None:
+    ptr = (lambda t: ctypes.c_void_p(t.data_ptr()))
+    sh = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    need = n_points * runs_per_point
+    if (d_per_run.numel() * d_per_run.element_size() < need * m * 8 or
+            d_best_height.numel() * d_best_height.element_size() < need * 4 or
+            d_pairs.numel() * d_pairs.element_size() < n_pairs * 16 or
+            d_cross.numel() * d_cross.element_size() < n_pairs * CROSS_WORDS * 8):
+        raise ValueError("a buffer is smaller than the launch reads or writes")
+    check(lib.msim_cross_launch(m, n_points, runs_per_point, ptr(d_per_run), ptr(d_best_height), ptr(d_pairs),
+                                n_pairs, ptr(d_cross), sh), "msim_cross_launch")
+
+
+def _run_contrasts(fn, what: str, handle, n_points: int, m: int, n_runs: int, pairs: Sequence[Pair], run_begin: int,
+                   seed_base: int, device: int) -> ContrastResult:
+    pairs = [Pair(*q) for q in pairs]
+    arr = pairs_struct(pairs, n_points, m)
+    cross = (MsimCross * len(pairs))()
+    points = _run_moments(
+        lambda h, b, n, sb, dev, stats, sums, mom, spec, counts: fn(h, b, n, sb, dev, arr, len(pairs), stats, sums,
+                                                                     mom, cross),
+        what, handle, n_points, m, n_runs, run_begin, seed_base, device, None)
+    words = np.ctypeslib.as_array(ctypes.cast(cross, ctypes.POINTER(ctypes.c_uint64)), shape=(len(pairs), CROSS_WORDS))
+    return ContrastResult(points=points, pairs=pairs, cross=cross_from_words(words), n_runs=n_runs)
 
 
 def _run_moments(fn, what: str, handle, n_points: int, m: int, n_runs: int, run_begin: int, seed_base: int,
@@ -227,6 +266,18 @@ class Simulation:
         """msim_moments_launch on the current device over a launch's records: d_per_run int32 [n_runs, M, 2],
         d_best_height int32 [n_runs], d_moments int64 [M, 20] and d_hist int64 [M, 2, bins + 2] (overwritten)."""
         _launch_moments(len(self.miners), 1, n_runs, d_per_run, d_best_height, d_moments, hist_spec, d_hist, stream)
+
+    def run_contrasts(self, n_runs: int, pairs: Sequence[Pair], run_begin: int = 0,
+                      seed_base: int = DEFAULT_SEED_BASE, device: int = 0) -> ContrastResult:
+        """msim_run_contrasts: run_moments() plus the exact cross sums of `pairs` (every pair within point 0, e.g.
+        pairs_between_miners(M)); contrasts(result) gives the differences between miners with standard errors."""
+        return _run_contrasts(lib.msim_run_contrasts, "msim_run_contrasts", self._h, 1, len(self.miners), n_runs,
+                              pairs, run_begin, seed_base, device)
+
+    def launch_cross(self, n_runs: int, d_per_run, d_best_height, d_pairs, n_pairs: int, d_cross, stream=None) -> None:
+        """msim_cross_launch on the current device over a launch's records: d_pairs int32 [n_pairs, 4] and d_cross
+        int64 [n_pairs, 12] (overwritten); the other buffers as launch_moments."""
+        _launch_cross(len(self.miners), 1, n_runs, d_per_run, d_best_height, d_pairs, n_pairs, d_cross, stream)
 
     def run_multi(self, n_runs: int, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
                   devices: Sequence[int] = (0,)) -> SimulationResult:
@@ -366,6 +417,20 @@ class Sweep:
         """msim_moments_launch over a sweep launch's records; d_moments int64 [n_points, M, 20]."""
         _launch_moments(self.m, len(self.sims), runs_per_point, d_per_run, d_best_height, d_moments, hist_spec,
                         d_hist, stream)
+
+    def run_contrasts(self, runs_per_point: int, pairs: Sequence[Pair], run_begin: int = 0,
+                      seed_base: int = DEFAULT_SEED_BASE, device: int = 0) -> ContrastResult:
+        """msim_sweep_run_contrasts: run_moments() plus the exact cross sums of `pairs` (e.g.
+        pairs_vs_baseline(len(sweep), M)). Every point runs on the same seeds, so contrasts(result) gives the
+        differences between points with the standard error of the per-run difference."""
+        return _run_contrasts(lib.msim_sweep_run_contrasts, "msim_sweep_run_contrasts", self._h, len(self.sims),
+                              self.m, runs_per_point, pairs, run_begin, seed_base, device)
+
+    def launch_cross(self, runs_per_point: int, d_per_run, d_best_height, d_pairs, n_pairs: int, d_cross,
+                     stream=None) -> None:
+        """msim_cross_launch over a sweep launch's records; d_pairs int32 [n_pairs, 4], d_cross int64 [n_pairs, 12]."""
+        _launch_cross(self.m, len(self.sims), runs_per_point, d_per_run, d_best_height, d_pairs, n_pairs, d_cross,
+                      stream)
 
     def workspace_bytes(self, runs_per_point: int) -> int:
         return int(lib.msim_sweep_workspace_bytes(self._h, runs_per_point))
