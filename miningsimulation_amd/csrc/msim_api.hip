@@ -227,31 +227,47 @@ msim::PipeLayout pipe_layout(const msim_config *c, uint64_t n_runs)
 int device_tables(msim_config *c, uint32_t seg, uint32_t nseg, msim::PipeTables *out)
 {
     using namespace msim;
-    const size_t pick_b = sizeof(PickTab), log_b = sizeof(LogTab), jump_b = (size_t)nseg * 128 * 16;
+    // K1's pick and log tables sit between the general ones and the jump matrices (sizes are multiples of 16
+    // bytes: the jump columns are read as uint4)
+    const size_t pick_b = sizeof(PickTab), log_b = sizeof(LogTab), k1_b = sizeof(PickTab) + sizeof(K1Log),
+                 jump_b = (size_t)nseg * 128 * 16;
+    static_assert((sizeof(PickTab) + sizeof(LogTab) + sizeof(PickTab) + sizeof(K1Log)) % 16 == 0, "jump table alignment");
     // an entry with the same segment length and at least as many segments serves: its jump table is a prefix
     const char *b = (const char *)c->tables.get(
-        TAB_PIPE + seg, nseg, [&](uint64_t have) { return have >= nseg; }, pick_b + log_b + jump_b,
+        TAB_PIPE + seg, nseg, [&](uint64_t have) { return have >= nseg; }, pick_b + log_b + k1_b + jump_b,
         [&](char *h, const char *) {
             build_pick_table(c->perc, c->prop, c->self, (int)c->n, (PickTab *)h);
             build_log_table((LogTab *)(h + pick_b));
-            build_jump_table(nseg, seg, (uint32_t *)(h + pick_b + log_b));
+            k1_tables_build(c->perc, c->prop, c->self, (int)c->n, (PickTab *)(h + pick_b + log_b),
+                            (K1Log *)(h + pick_b + log_b + pick_b));
+            build_jump_table(nseg, seg, (uint32_t *)(h + pick_b + log_b + k1_b));
         });
     if (!b) return MSIM_E_HIP;
     out->pick = (const PickTab *)b;
     out->logt = (const LogTab *)(b + pick_b);
-    out->jump = (const uint32_t *)(b + pick_b + log_b);
+    out->k1pick = (const PickTab *)(b + pick_b + log_b);
+    out->k1log = (const K1Log *)(b + pick_b + log_b + pick_b);
+    out->jump = (const uint32_t *)(b + pick_b + log_b + k1_b);
+    out->k1_fthr = 0;
+    out->k1_uni = k1_tables_uniform(c->prop, c->self, (int)c->n, &out->k1_fthr) ? 1u : 0u;
     return MSIM_OK;
 }
 
 // Process-wide log table (msim_fastdraw.h) per device, for msim_device_intervals and the entity engine. It
 // lives as long as the process: the cache is never destroyed.
-int global_log_table(const msim::LogTab **out)
+// K1's log table follows it in the same entry (msim_device_intervals checks K1's form of the interval too).
+int global_log_table(const msim::LogTab **out, const msim::K1Log **k1 = nullptr)
 {
     static std::mutex mu;
     static TableCache *cache = new TableCache(mu);
-    *out = (const msim::LogTab *)cache->get(0, sizeof(msim::LogTab),
-                                            [](char *h, const char *) { msim::build_log_table((msim::LogTab *)h); });
-    return *out ? MSIM_OK : MSIM_E_HIP;
+    static_assert(sizeof(msim::LogTab) % 8 == 0, "K1Log alignment");
+    const char *b = (const char *)cache->get(0, sizeof(msim::LogTab) + sizeof(msim::K1Log), [](char *h, const char *) {
+        msim::build_log_table((msim::LogTab *)h);
+        msim::k1_log_build((msim::K1Log *)(h + sizeof(msim::LogTab)));
+    });
+    *out = (const msim::LogTab *)b;
+    if (k1) *k1 = b ? (const msim::K1Log *)(b + sizeof(msim::LogTab)) : nullptr;
+    return b ? MSIM_OK : MSIM_E_HIP;
 }
 
 constexpr double WIDE_SLICE_BUDGET = 16.0 * (1ull << 30);
@@ -984,9 +1000,10 @@ int msim_device_intervals(const uint64_t *d_uniform, int64_t *d_out_ms, uint64_t
 {
     if (!d_uniform || !d_out_ms) return MSIM_E_INVALID;
     const msim::LogTab *lt = nullptr;
-    const int rc = global_log_table(&lt);
+    const msim::K1Log *kl = nullptr;
+    const int rc = global_log_table(&lt, &kl);
     if (rc) return rc;
-    return msim::launch_intervals(lt, d_uniform, d_out_ms, n, (hipStream_t)stream) == hipSuccess ? MSIM_OK : MSIM_E_HIP;
+    return msim::launch_intervals(lt, kl, d_uniform, d_out_ms, n, (hipStream_t)stream) == hipSuccess ? MSIM_OK : MSIM_E_HIP;
 }
 
 int msim_device_picks(const msim_config *cfg, const uint64_t *d_uniform, int32_t *d_out_index, uint64_t n, void *stream)

@@ -43,12 +43,12 @@ struct DevCtx {
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshl_add_u32 %0, %0, 2, %1"
                      : "=&v"(cbase) : "s"(wbase));
     }
-    // owner row k = info_finder(info) sits at byte offset k << 10 = info & (15 << INFO_K_SHIFT)
-    __device__ __forceinline__ void count(uint32_t info)
+    // row = the byte offset of owner k's counter row, k << 10 (K1Draws::row: info & (15 << INFO_K_SHIFT), or the
+    // pick entry itself in the uniform-delay form)
+    __device__ __forceinline__ void count(uint32_t row)
     {
         // the array's base is a constant the compiler folds into the instruction's offset field
-        const uint32_t ad = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&cnt[0][0] +
-                            ((info & (15u << INFO_K_SHIFT)) | cbase);
+        const uint32_t ad = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&cnt[0][0] + (row | cbase);
         __atomic_fetch_add((__attribute__((address_space(3))) uint32_t *)(uintptr_t)ad, 1u, __ATOMIC_RELAXED);
     }
     __device__ __forceinline__ bool vote(bool s) const { return (__builtin_amdgcn_ballot_w64(s) & amask) != 0ull; }
@@ -139,25 +139,30 @@ struct DevCtx {
 // (c2, profiles/r03/INDEX.md): 4 waves (113 VGPRs) 4.17 ms, 5 (96) 4.02 ms, 6 (80) 3.75 ms, 7 (72) 7.3 ms and
 // 8 (64) 13.7 ms, where the spills reach the draw loop's hot values. Re-measured on round 5's K1 (chunked list
 // reservation; profiles/r05/k1waves): 4 waves (104 VGPRs) 3.27 ms, 5 (96, 10 spills) 3.17-3.21 ms, 6 (80, 23
-// spills) 3.27 ms serial, same box, alternating.
+// spills) 3.27 ms serial, same box, alternating. Re-measured on round 7's loop (K1's own interval form, 12 fewer
+// VALU instructions per block; profiles/r07/INDEX.md): 4 waves (102 VGPRs, no scratch) 11.40 M run-years/s serial
+// and 12.41 M on two streams, 5 (96, 8 spills) 11.38 M / 12.32 M, 6 (80) 11.01 M / 12.48 M: 4 is the only budget
+// that is at or near the top of both lines.
 #ifndef MSIM_K1_WAVES
-#define MSIM_K1_WAVES 5
+#define MSIM_K1_WAVES 4
 #endif
+// UNI: the uniform-delay form (K1Draws<true>; launch_draws picks it from the tables' k1_uni).
+template <bool UNI>
 #if MSIM_K1_WAVES
 __global__ __launch_bounds__(256, MSIM_K1_WAVES) void msim_draws_kernel(const DrawArgs a)
 #else
 __global__ __launch_bounds__(256) void msim_draws_kernel(const DrawArgs a)
 #endif
 {
-    // one LDS block: pick table, log table, owner counters
+    // one LDS block: pick table, log table, owner counters (26 KB: up to six workgroups per CU fit in 160 KB)
     __shared__ struct {
         PickTab pick;
-        LogTab log;
+        K1Log log;
         uint32_t cnt[K1_ROWS][256];
     } sm;
     const uint32_t tid = threadIdx.x;
-    for (uint32_t i = tid; i < sizeof(PickTab) / 4; i += 256) ((uint32_t *)&sm.pick)[i] = ((const uint32_t *)a.tab.pick)[i];
-    for (uint32_t i = tid; i < sizeof(LogTab) / 8; i += 256) ((double *)&sm.log)[i] = ((const double *)a.tab.logt)[i];
+    for (uint32_t i = tid; i < sizeof(PickTab) / 4; i += 256) ((uint32_t *)&sm.pick)[i] = ((const uint32_t *)a.tab.k1pick)[i];
+    for (uint32_t i = tid; i < sizeof(K1Log) / 8; i += 256) ((double *)&sm.log)[i] = ((const double *)a.tab.k1log)[i];
     auto s_cnt = sm.cnt;
 #pragma unroll
     for (uint32_t w = 0; w < K1_ROWS; ++w) s_cnt[w][tid] = 0;
@@ -174,7 +179,7 @@ __global__ __launch_bounds__(256) void msim_draws_kernel(const DrawArgs a)
     DevCtx cx{a, s_cnt, __builtin_amdgcn_ballot_w64(r < a.n), tid, (uint32_t)__builtin_amdgcn_readfirstlane(r & ~63u), seg,
               seg - a.band_lo, 0u,
               (uint32_t)__builtin_amdgcn_readfirstlane((tid & ~63u) * 4u), 0u, 0u};
-    const uint64_t tsum = draw_segment<DevCtx>(cx, ri, rp, &sm.log, &sm.pick, b0, a.seg, seg >= a.band_lo);
+    const uint64_t tsum = draw_segment_k1<UNI, DevCtx>(cx, ri, rp, &sm.log, &sm.pick, a.tab.k1_fthr, b0, a.seg, seg >= a.band_lo);
     cx.holes();
     a.segsum[(size_t)seg * a.nr + r] = tsum;
 #pragma unroll
@@ -182,13 +187,22 @@ __global__ __launch_bounds__(256) void msim_draws_kernel(const DrawArgs a)
     a.nslow[(size_t)seg * a.nr + r] = s_cnt[K1_NSL][tid];
 }
 
-__global__ void msim_interval_kernel(const LogTab *__restrict__ lt, const uint64_t *__restrict__ u,
-                                     int64_t *__restrict__ out, uint64_t n)
+// Intervals of given uniforms by K1's chain (its fast form, then the general form, then glibc's sequence); every
+// eighth input takes the general tables' chain (interval_ms_fast, what K2, K3 and the engines draw with) instead,
+// so a test over crafted inputs covers both.
+__global__ void msim_interval_kernel(const LogTab *__restrict__ lt, const K1Log *__restrict__ kl,
+                                     const uint64_t *__restrict__ u, int64_t *__restrict__ out, uint64_t n)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     bool ok;
-    const int32_t q = interval_ms_fast(u[i], lt, ok);
+    int32_t q;
+    if ((i & 7u) == 7u) {
+        q = interval_ms_fast(u[i], lt, ok);
+    } else {
+        q = k1_interval_fast(u[i], kl, ok);
+        if (!ok) q = k1_interval_general(u[i], kl, ok);
+    }
     out[i] = ok ? q : interval_ms_exact_dev(u[i]);
 }
 
@@ -201,10 +215,10 @@ __global__ void msim_pick_kernel(const PickTab *__restrict__ pt, const uint64_t 
     out[i] = k == 15u ? -1 : (int32_t)k;
 }
 
-hipError_t launch_intervals(const LogTab *lt, const uint64_t *u, int64_t *out, uint64_t n, hipStream_t s)
+hipError_t launch_intervals(const LogTab *lt, const K1Log *kl, const uint64_t *u, int64_t *out, uint64_t n, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(msim_interval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lt, u, out, n);
+    hipLaunchKernelGGL(msim_interval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lt, kl, u, out, n);
     return hipGetLastError();
 }
 
@@ -217,13 +231,32 @@ hipError_t launch_picks(const PickTab *pt, const uint64_t *u, int32_t *out, uint
 
 hipError_t draws_blocks_per_cu(int *blocks)
 {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, msim_draws_kernel, 256, 0);
+    int u = 0, g = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&u, msim_draws_kernel<true>, 256, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&g, msim_draws_kernel<false>, 256, 0);
+    *blocks = u < g ? u : g;
+    return e;
 }
 
 hipError_t launch_draws(const DrawArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(msim_draws_kernel, dim3(a.nr / 256, a.nseg), dim3(256), 0, s, a);
+    if (a.tab.k1_uni) hipLaunchKernelGGL(msim_draws_kernel<true>, dim3(a.nr / 256, a.nseg), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(msim_draws_kernel<false>, dim3(a.nr / 256, a.nseg), dim3(256), 0, s, a);
     return hipGetLastError();
 }
+
+// K1's tables are built here, in K1's translation unit, so that a variant build of this file alone (Makefile
+// `variant`) gets tables that match its switches (MSIM_FD_A2, MSIM_FD_DEG4, MSIM_K1_UNI).
+void k1_tables_build(const uint64_t *perc, const int64_t *prop, const uint8_t *selfish, int m, PickTab *pick, K1Log *log)
+{
+    uint32_t fthr = 0;
+    build_k1_pick(perc, prop, selfish, m, k1_uniform_fthr(prop, selfish, m, &fthr), pick);
+    build_k1_log(log);
+}
+bool k1_tables_uniform(const int64_t *prop, const uint8_t *selfish, int m, uint32_t *fthr)
+{
+    return k1_uniform_fthr(prop, selfish, m, fthr);
+}
+void k1_log_build(K1Log *log) { build_k1_log(log); }
 
 }  // namespace msim

@@ -94,6 +94,11 @@ struct PipeTables {
     const PickTab *pick;
     const LogTab *logt;
     const uint32_t *jump;  // nseg * 128 columns of 4 words
+    // K1's own tables (msim_fastdraw.h, "K1's form"; built by k1_tables_build in K1's translation unit)
+    const PickTab *k1pick;
+    const K1Log *k1log;
+    uint32_t k1_uni;   // 1: every miner honest with the fast threshold k1_fthr (K1's uniform-delay instantiation)
+    uint32_t k1_fthr;
 };
 
 struct DrawArgs {
@@ -303,8 +308,120 @@ MSIM_HD void draw_quad_exact(Rng ri, Rng rp, const LogTab *__restrict__ lt, cons
     }
 }
 
-// One (run, segment) worker: SEG blocks from the jumped RNG states. Ctx supplies the side effects:
-//   count(info)                       per-owner counter of this lane (+1 for owner info_finder(info))
+// K1's own forms of the same draws (msim_fastdraw.h, "K1's form"): any 64-bit draw still gets the reference's
+// interval and finder.
+MSIM_HD uint32_t k1_draw_interval(Rng &ri, const K1Log *__restrict__ kl, FdConsts kc)
+{
+    const uint64_t u = rng_next(ri);
+    bool ok;
+    const int32_t q = k1_interval_general(u, kl, ok, kc);
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)(ok ? q : interval_ms_exact_dev(u));
+#else
+    return (uint32_t)(ok ? q : (int32_t)interval_ms_of(u));
+#endif
+}
+// As draw_quad_fast. The exponent limit of the folded table is checked once per quad: the smallest high word
+// of the four v's (shifted: vt) against FD_VT_MIN.
+MSIM_HD bool k1_quad_fast(Rng &ri, Rng &rp, const K1Log *__restrict__ kl, const PickTab *__restrict__ kp, FdConsts kc,
+                          uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB])
+{
+    uint32_t ki = 0, kk = 0, vmin = 0xFFFFFFFFu;
+#pragma unroll
+    for (int q = 0; q < K1_QB; ++q) {
+        const uint64_t ui = rng_next(ri), up = rng_next(rp);
+        uint32_t a, b, vt;
+        I[q] = (uint32_t)k1_interval_key<MSIM_FD_A2 != 0>(ui, kl, a, vt, kc);
+        info[q] = kp->info[pick_q_fast_key(up, b)];
+        ki = a > ki ? a : ki;
+        kk = b > kk ? b : kk;
+        vmin = vt < vmin ? vt : vmin;
+    }
+    return ki >= K1_OK_RANGE || kk >= PICK_RARE_LO || (MSIM_FD_A2 && vmin < FD_VT_MIN);
+}
+// The redraw of a flagged quad: every interval by the general form first (3e-5 of draws only left the folded
+// table's exponent range), glibc's sequence for the one within the margin of a millisecond boundary.
+MSIM_HD void k1_quad_exact(Rng ri, Rng rp, const K1Log *__restrict__ kl, const PickTab *__restrict__ kp, FdConsts kc,
+                           uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB])
+{
+#pragma unroll
+    for (int q = 0; q < K1_QB; ++q) {
+        I[q] = k1_draw_interval(ri, kl, kc);
+        info[q] = kp->info[pick_q_exact(rng_next(rp))];
+    }
+}
+
+// The draw forms behind draw_segment_with: the first block's draws, a quad of fast draws with its exactness
+// flag, the quad's exact redraw, a block's fast bit and the counter row count() is called with.
+// GeneralDraws: the general tables (what K2 and K3 redraw with; the host checks run the lane body on it).
+struct GeneralDraws {
+    const LogTab *lt;
+    const PickTab *pt;
+    FdConsts kc;
+    MSIM_HD void begin() { kc = fd_consts(); }
+    MSIM_HD FdConsts quad_consts() const { return kc; }
+    MSIM_HD uint32_t interval(Rng &ri) const { return draw_interval(ri, lt, kc); }
+    MSIM_HD uint32_t pick(Rng &rp) const { return pick_info(rng_next(rp), pt); }
+    MSIM_HD bool quad_fast(Rng &ri, Rng &rp, FdConsts kq, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
+    {
+        return draw_quad_fast(ri, rp, lt, pt, kq, I, info);
+    }
+    MSIM_HD void quad_exact(const Rng &ri, const Rng &rp, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
+    {
+        draw_quad_exact(ri, rp, lt, pt, I, info);
+    }
+    MSIM_HD bool slow(uint32_t next, uint32_t info) const { return next <= info_fthr(info); }
+    MSIM_HD uint32_t row(uint32_t info) const { return info; }
+};
+// K1Draws: K1's tables. UNI (k1_uniform_fthr): one scalar fast threshold, and the pick entry IS the row offset.
+template <bool UNI>
+struct K1Draws {
+    const K1Log *kl;
+    const PickTab *kp;  // build_k1_pick(uni = UNI)
+    uint32_t fthr;      // UNI: every finder's fast threshold
+    FdConsts kc;
+    MSIM_HD void begin()
+    {
+        kc = MSIM_K1_CONSTS;
+#if defined(__HIP_DEVICE_COMPILE__)
+        // all coefficients in SGPRs; the leading one reaches a VGPR per quad (quad_consts)
+        asm("" : "+s"(kc.c1));
+        asm("" : "+s"(kc.c2));
+        asm("" : "+s"(kc.c3));
+        asm("" : "+s"(kc.c4));
+#if !MSIM_FD_DEG4
+        asm("" : "+s"(kc.c5));
+#endif
+#endif
+    }
+    MSIM_HD FdConsts quad_consts() const
+    {
+        FdConsts kq = kc;
+#if defined(__HIP_DEVICE_COMPILE__)
+        // the polynomial's leading coefficient, a VGPR operand (one VOP3 reads at most one SGPR), copied from
+        // its SGPR each quad (one v_mov_b64) instead of being held across the loop, where the register budget
+        // of K1 sent it to scratch
+        asm volatile("v_mov_b64 %0, %1" : "=v"(kq.MSIM_K1_LEAD) : "s"(kc.MSIM_K1_LEAD));
+#endif
+        return kq;
+    }
+    MSIM_HD uint32_t interval(Rng &ri) const { return k1_draw_interval(ri, kl, kc); }
+    MSIM_HD uint32_t pick(Rng &rp) const { return kp->info[pick_q_exact(rng_next(rp))]; }
+    MSIM_HD bool quad_fast(Rng &ri, Rng &rp, FdConsts kq, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
+    {
+        return k1_quad_fast(ri, rp, kl, kp, kq, I, info);
+    }
+    MSIM_HD void quad_exact(const Rng &ri, const Rng &rp, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
+    {
+        k1_quad_exact(ri, rp, kl, kp, kc, I, info);
+    }
+    MSIM_HD bool slow(uint32_t next, uint32_t info) const { return next <= (UNI ? fthr : info_fthr(info)); }
+    MSIM_HD uint32_t row(uint32_t info) const { return UNI ? info : info & (15u << INFO_K_SHIFT); }
+};
+
+// One (run, segment) worker: SEG blocks from the jumped RNG states. `d` is the draw form (above). Ctx supplies
+// the side effects:
+//   count(row)                        per-owner counter of this lane (+1 for owner info_finder(row); row = d.row(info))
 //   vote(s)                           nonzero when s holds for some active lane of the wave (host: s)
 //   slow(s, block, offset, w0, w1, ri, rp, skip)
 //                                     called after a nonzero vote: records a non-fast block when s
@@ -319,22 +436,12 @@ MSIM_HD void draw_quad_exact(Rng ri, Rng rp, const LogTab *__restrict__ lt, cons
 // Blocks are drawn four at a time (draw_quad_fast); the streams after a block inside a quad, needed only
 // by the rare non-fast block, are re-stepped from the quad's start. Time is summed per group in 32 bits
 // (32 intervals < 2^25 ms each) and folded into 64 bits per group.
-template <class Ctx>
-MSIM_HD uint64_t draw_segment(Ctx &cx, Rng &ri, Rng &rp, const LogTab *__restrict__ lt,
-                              const PickTab *__restrict__ pt, uint32_t b0, uint32_t seg, bool band)
+template <class Ctx, class Draws>
+MSIM_HD uint64_t draw_segment_with(Ctx &cx, Draws &d, Rng &ri, Rng &rp, uint32_t b0, uint32_t seg, bool band)
 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    FdConsts kc{FD_C1, FD_C2, FD_C3, FD_C4, FD_C5};  // all five in SGPRs; c5 reaches a VGPR per quad (below)
-    asm("" : "+s"(kc.c1));
-    asm("" : "+s"(kc.c2));
-    asm("" : "+s"(kc.c3));
-    asm("" : "+s"(kc.c4));
-    asm("" : "+s"(kc.c5));
-#else
-    const FdConsts kc = fd_consts();
-#endif
-    uint32_t Icur = draw_interval(ri, lt, kc);
-    uint32_t infocur = pick_info(rng_next(rp), pt);
+    d.begin();
+    uint32_t Icur = d.interval(ri);
+    uint32_t infocur = d.pick(rp);
     uint64_t tsum = 0;
     for (uint32_t g = 0; g < seg / GROUP; ++g) {
         if (band) cx.group_start(g, (Icur << 5) | info_finder(infocur), ri, rp);
@@ -342,26 +449,19 @@ MSIM_HD uint64_t draw_segment(Ctx &cx, Rng &ri, Rng &rp, const LogTab *__restric
         for (uint32_t q4 = 0; q4 < GROUP / K1_QB; ++q4) {
             uint32_t I[K1_QB], info[K1_QB];
             cx.quad();  // per-quad values the context rebuilds rather than holding across the loop
-#if defined(__HIP_DEVICE_COMPILE__)
-            // the polynomial's leading coefficient, a VGPR operand (one VOP3 reads at most one SGPR), copied
-            // from its SGPR each quad (one v_mov_b64) instead of being held across the loop, where the register
-            // budget of K1 sent it to scratch
-            FdConsts kq = kc;
-            asm volatile("v_mov_b64 %0, %1" : "=v"(kq.c5) : "s"(kc.c5));
-#else
-            const FdConsts kq = kc;
-#endif
-            // The quad's start states are read only on the two rare paths below; at K1's register budget (96
-            // VGPRs at 5 waves per SIMD, msim_drawgen.hip) the compiler keeps them in scratch, written once per quad.
-            // Measured on MI355X: recovering them by inverse stepping instead (no scratch, 84 VGPRs) made K1
-            // 11 % slower at the same occupancy (profiles/r03/INDEX.md, k1 A/B).
+            const FdConsts kq = d.quad_consts();
+            // The quad's start states are read only on the two rare paths below; at a register budget of 96 VGPRs
+            // or fewer (5 or more waves per SIMD, msim_drawgen.hip) the compiler keeps them in scratch, written
+            // once per quad; at the shipped 4 waves they stay in registers. Measured on MI355X: recovering them by
+            // inverse stepping instead (no scratch, 84 VGPRs) made K1 11 % slower at the same occupancy
+            // (profiles/r03/INDEX.md, k1 A/B).
             const Rng ri0 = ri, rp0 = rp;
-            if (draw_quad_fast(ri, rp, lt, pt, kq, I, info)) draw_quad_exact(ri0, rp0, lt, pt, I, info);
+            if (d.quad_fast(ri, rp, kq, I, info)) d.quad_exact(ri0, rp0, I, info);
 #pragma unroll
             for (int q = 0; q < K1_QB; ++q) {
                 gacc += Icur;
-                const bool slow = I[q] <= info_fthr(infocur);  // I_{i+1} vs the finder's delay
-                cx.count(infocur);
+                const bool slow = d.slow(I[q], infocur);  // I_{i+1} vs the finder's delay
+                cx.count(d.row(infocur));
                 if (cx.vote(slow))  // the streams after block i+1 are the quad's start + q + 1 draws (K2 steps them)
                     cx.slow(slow, b0 + g * GROUP + q4 * K1_QB + (uint32_t)q, tsum + gacc, (Icur << 5) | info_finder(infocur),
                             (I[q] << 5) | info_finder(info[q]), ri0, rp0, (uint32_t)q + 1u);
@@ -373,6 +473,22 @@ MSIM_HD uint64_t draw_segment(Ctx &cx, Rng &ri, Rng &rp, const LogTab *__restric
         tsum += gacc;
     }
     return tsum;
+}
+// The lane body on the general tables.
+template <class Ctx>
+MSIM_HD uint64_t draw_segment(Ctx &cx, Rng &ri, Rng &rp, const LogTab *__restrict__ lt,
+                              const PickTab *__restrict__ pt, uint32_t b0, uint32_t seg, bool band)
+{
+    GeneralDraws d{lt, pt, MSIM_FD_DEFAULT};
+    return draw_segment_with(cx, d, ri, rp, b0, seg, band);
+}
+// The lane body as K1 runs it (msim_drawgen.hip): K1's tables, uniform-delay form when uni.
+template <bool UNI, class Ctx>
+MSIM_HD uint64_t draw_segment_k1(Ctx &cx, Rng &ri, Rng &rp, const K1Log *__restrict__ kl,
+                                 const PickTab *__restrict__ kp, uint32_t fthr, uint32_t b0, uint32_t seg, bool band)
+{
+    K1Draws<UNI> d{kl, kp, fthr, MSIM_K1_CONSTS};
+    return draw_segment_with(cx, d, ri, rp, b0, seg, band);
 }
 
 // ---------------------------------------------------------------- K3 lane body (shared host/device)
