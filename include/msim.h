@@ -171,7 +171,14 @@ int msim_launch(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uin
  *                         through the draw kernel's production path (msim_fastdraw.h + exact fallback)
  *   msim_device_picks     PickFinder index of given uniform u64 draws (simulation.h:213-221), through
  *                         the draw kernel's table lookup; -1 where the reference would assert
+ *   msim_device_k1_quads  the draw kernel's quad of four blocks (its fast draws, then their exact redraw when the
+ *                         quad is flagged) from n pairs of xoroshiro128++ states: d_states holds s0, s1 of the
+ *                         interval stream and s0, s1 of the picker stream per quad; d_out receives per quad
+ *                         the four intervals in ms, then the four finders (15 where PickFinder falls through).
+ *                         Honest networks of the pipeline only; the kernel's uniform-delay or per-finder
+ *                         instantiation is chosen as for a run of cfg
  * All pointers are device memory; launches go to `stream` (hipStream_t, NULL = default). */
+int msim_device_k1_quads(const msim_config *cfg, const uint64_t *d_states, uint32_t *d_out, uint64_t n, void *stream);
 int msim_device_log1p(const double *d_x, double *d_out, uint64_t n, void *stream);
 int msim_device_intervals(const uint64_t *d_uniform, int64_t *d_out_ms, uint64_t n, void *stream);
 int msim_device_picks(const msim_config *cfg, const uint64_t *d_uniform, int32_t *d_out_index, uint64_t n,

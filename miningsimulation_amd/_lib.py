@@ -43,6 +43,7 @@ EXPORTED = (
     "msim_device_log1p",
     "msim_device_intervals",
     "msim_device_picks",
+    "msim_device_k1_quads",  # test surface: bound where it is used (tests/test_gpu_k1_quads.py)
     "msim_sums_to_stats",
     "msim_timing_enable",
     "msim_timing_read",

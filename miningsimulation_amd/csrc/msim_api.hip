@@ -260,7 +260,7 @@ int global_log_table(const msim::LogTab **out, const msim::K1Log **k1 = nullptr)
 {
     static std::mutex mu;
     static TableCache *cache = new TableCache(mu);
-    static_assert(sizeof(msim::LogTab) % 8 == 0, "K1Log alignment");
+    static_assert(sizeof(msim::LogTab) % alignof(msim::K1Log) == 0, "K1Log alignment");
     const char *b = (const char *)cache->get(0, sizeof(msim::LogTab) + sizeof(msim::K1Log), [](char *h, const char *) {
         msim::build_log_table((msim::LogTab *)h);
         msim::k1_log_build((msim::K1Log *)(h + sizeof(msim::LogTab)));
@@ -1021,6 +1021,18 @@ int msim_device_picks(const msim_config *cfg, const uint64_t *d_uniform, int32_t
     const int rc = device_tables(const_cast<msim_config *>(cfg), pl.seg, pl.nseg, &t);
     if (rc) return rc;
     return msim::launch_picks(t.pick, d_uniform, d_out_index, n, (hipStream_t)stream) == hipSuccess ? MSIM_OK : MSIM_E_HIP;
+}
+
+int msim_device_k1_quads(const msim_config *cfg, const uint64_t *d_states, uint32_t *d_out, uint64_t n, void *stream)
+{
+    if (!cfg || !d_states || !d_out || cfg->wide) return MSIM_E_INVALID;
+    msim::PipeTables t;
+    const msim::PipeLayout pl = pipe_layout(cfg, 1);
+    const int rc = device_tables(const_cast<msim_config *>(cfg), pl.seg, pl.nseg, &t);
+    if (rc) return rc;
+    static_assert(sizeof(msim::Rng) == 16, "two 64-bit words per stream state");
+    return msim::launch_k1_quads(t, (const msim::Rng *)d_states, d_out, n, (hipStream_t)stream) == hipSuccess ? MSIM_OK
+                                                                                                             : MSIM_E_HIP;
 }
 
 // A Q32.32 sum held as two limbs -> double with ONE rounding of the exact value (hi << 32) + lo, so the

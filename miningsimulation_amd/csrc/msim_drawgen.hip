@@ -36,12 +36,13 @@ struct DevCtx {
     uint32_t (*cnt)[256];
     uint64_t amask;  // active lanes of the wave (runs < n)
     uint32_t tid, r0, seg, jb;  // r0: the wave's first run (wave-uniform)
-    uint32_t cbase;             // tid * 4, rebuilt every quad (quad())
-    uint32_t wbase;             // 4 x the wave's first thread (SGPR)
-    __device__ __forceinline__ void quad()
+    uint32_t cbase;             // tid * 4, the lane's byte offset in a counter row (hold())
+    // The one lane-dependent value held across the loop: at 4 waves per SIMD the budget has the register, and
+    // rebuilding it (two v_mbcnt and a shift-add per quad, as the 5- and 6-wave budgets needed) cost 0.75 VALU a block.
+    __device__ __forceinline__ void hold()
     {
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshl_add_u32 %0, %0, 2, %1"
-                     : "=&v"(cbase) : "s"(wbase));
+        cbase = tid * 4u;
+        asm volatile("" : "+v"(cbase));  // a register of its own, not an expression to rebuild at each use
     }
     // row = the byte offset of owner k's counter row, k << 10 (K1Draws::row: info & (15 << INFO_K_SHIFT), or the
     // pick entry itself in the uniform-delay form)
@@ -142,7 +143,8 @@ struct DevCtx {
 // spills) 3.27 ms serial, same box, alternating. Re-measured on round 7's loop (K1's own interval form, 12 fewer
 // VALU instructions per block; profiles/r07/INDEX.md): 4 waves (102 VGPRs, no scratch) 11.40 M run-years/s serial
 // and 12.41 M on two streams, 5 (96, 8 spills) 11.38 M / 12.32 M, 6 (80) 11.01 M / 12.48 M: 4 is the only budget
-// that is at or near the top of both lines.
+// that is at or near the top of both lines. Round 8's loop spends the slack of that budget on values held across the
+// loop (DevCtx::hold, K1Draws::begin): 105 VGPRs, no scratch (profiles/r08/INDEX.md).
 #ifndef MSIM_K1_WAVES
 #define MSIM_K1_WAVES 4
 #endif
@@ -154,15 +156,22 @@ __global__ __launch_bounds__(256, MSIM_K1_WAVES) void msim_draws_kernel(const Dr
 __global__ __launch_bounds__(256) void msim_draws_kernel(const DrawArgs a)
 #endif
 {
-    // one LDS block: pick table, log table, owner counters (26 KB: up to six workgroups per CU fit in 160 KB)
+    // one LDS block: the packed log table, invc and row e = 0 of A2 (the general-form redraw), pick table, owner
+    // counters (34.5 KB: four workgroups per CU, the register budget's count, fit in 160 KB)
     __shared__ struct {
+        K1Pair P[K1_EROWS * LOG_TAB];
+        double invc[LOG_TAB], A0[LOG_TAB];
         PickTab pick;
-        K1Log log;
         uint32_t cnt[K1_ROWS][256];
     } sm;
     const uint32_t tid = threadIdx.x;
+    const K1Log *kl = a.tab.k1log;
     for (uint32_t i = tid; i < sizeof(PickTab) / 4; i += 256) ((uint32_t *)&sm.pick)[i] = ((const uint32_t *)a.tab.k1pick)[i];
-    for (uint32_t i = tid; i < sizeof(K1Log) / 8; i += 256) ((double *)&sm.log)[i] = ((const double *)a.tab.k1log)[i];
+    for (uint32_t i = tid; i < K1_EROWS * LOG_TAB; i += 256) sm.P[i] = kl->P[i];
+    if (tid < LOG_TAB) {
+        sm.invc[tid] = kl->invc[tid];
+        sm.A0[tid] = kl->A2[(K1_EROWS - 1) * LOG_TAB + tid];
+    }
     auto s_cnt = sm.cnt;
 #pragma unroll
     for (uint32_t w = 0; w < K1_ROWS; ++w) s_cnt[w][tid] = 0;
@@ -177,9 +186,10 @@ __global__ __launch_bounds__(256) void msim_draws_kernel(const DrawArgs a)
 
     const uint32_t b0 = seg * a.seg;
     DevCtx cx{a, s_cnt, __builtin_amdgcn_ballot_w64(r < a.n), tid, (uint32_t)__builtin_amdgcn_readfirstlane(r & ~63u), seg,
-              seg - a.band_lo, 0u,
-              (uint32_t)__builtin_amdgcn_readfirstlane((tid & ~63u) * 4u), 0u, 0u};
-    const uint64_t tsum = draw_segment_k1<UNI, DevCtx>(cx, ri, rp, &sm.log, &sm.pick, a.tab.k1_fthr, b0, a.seg, seg >= a.band_lo);
+              seg - a.band_lo, 0u, 0u, 0u};
+    cx.hold();
+    const uint64_t tsum =
+        draw_segment_k1_on<UNI, DevCtx>(cx, ri, rp, sm.P, sm.invc, sm.A0, &sm.pick, a.tab.k1_fthr, b0, a.seg, seg >= a.band_lo);
     cx.holes();
     a.segsum[(size_t)seg * a.nr + r] = tsum;
 #pragma unroll
@@ -200,7 +210,7 @@ __global__ void msim_interval_kernel(const LogTab *__restrict__ lt, const K1Log 
     if ((i & 7u) == 7u) {
         q = interval_ms_fast(u[i], lt, ok);
     } else {
-        q = k1_interval_fast(u[i], kl, ok);
+        q = k1p_interval_fast(u[i], kl->P, ok);
         if (!ok) q = k1_interval_general(u[i], kl, ok);
     }
     out[i] = ok ? q : interval_ms_exact_dev(u[i]);
@@ -213,6 +223,37 @@ __global__ void msim_pick_kernel(const PickTab *__restrict__ pt, const uint64_t 
     if (i >= n) return;
     const uint32_t k = info_finder(pick_info(u[i], pt));
     out[i] = k == 15u ? -1 : (int32_t)k;
+}
+
+// K1's quad from given start states (msim_device_k1_quads, a test entry): the draw form's quad_fast, then its
+// quad_exact when flagged, exactly as the lane body calls them. st[2 i], st[2 i + 1]: the interval and the picker
+// stream; out[8 i ..]: the four intervals, then the four finders (15: PickFinder fell through).
+template <bool UNI>
+__global__ void msim_k1_quads_kernel(const PickTab *__restrict__ kp, const K1Log *__restrict__ kl, uint32_t fthr,
+                                     const Rng *__restrict__ st, uint32_t *__restrict__ out, uint64_t n)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    K1Draws<UNI> d{kl->P, kl->invc, kl->A2 + (K1_EROWS - 1) * LOG_TAB, kp, fthr, MSIM_K1_CONSTS};
+    d.begin();
+    Rng ri = st[2 * i], rp = st[2 * i + 1];
+    const Rng ri0 = ri, rp0 = rp;
+    uint32_t I[K1_QB], info[K1_QB];
+    if (d.quad_fast(ri, rp, I, info)) d.quad_exact(ri0, rp0, I, info);
+#pragma unroll
+    for (int q = 0; q < K1_QB; ++q) {
+        out[8 * i + q] = I[q];
+        out[8 * i + K1_QB + q] = info_finder(info[q]);
+    }
+}
+
+hipError_t launch_k1_quads(const PipeTables &t, const Rng *st, uint32_t *out, uint64_t n, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (t.k1_uni) hipLaunchKernelGGL(msim_k1_quads_kernel<true>, grid, dim3(256), 0, s, t.k1pick, t.k1log, t.k1_fthr, st, out, n);
+    else hipLaunchKernelGGL(msim_k1_quads_kernel<false>, grid, dim3(256), 0, s, t.k1pick, t.k1log, t.k1_fthr, st, out, n);
+    return hipGetLastError();
 }
 
 hipError_t launch_intervals(const LogTab *lt, const K1Log *kl, const uint64_t *u, int64_t *out, uint64_t n, hipStream_t s)

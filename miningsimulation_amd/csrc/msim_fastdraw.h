@@ -177,7 +177,7 @@ MSIM_HD int32_t interval_ms_fast(uint64_t u, const LogTab *__restrict__ tab, boo
 //   replaces the exponent's extraction, its conversion and the last FMA. Row eps = (e + 1023) & 15 holds
 //   e = eps - 15, right for e in [-15, 0]; a smaller exponent (2^-15 of draws) aliases and MUST be rejected:
 //   the caller checks vt = vh >> 11 (the table offset before masking, which the form computes anyway)
-//   against FD_VT_MIN (k1_quad_fast folds a min of vt over the quad into one compare).
+//   against FD_VT_MIN (K1's quad, msim_pipeline.h k1p_quad_fast, folds a min over the quad into one compare).
 // MSIM_FD_DEG4: -6e5 log1p(r) as the degree-4 minimax polynomial of scripts/fit_log1p_deg4.py (Remez, 60
 //   digits; k1..k4 rounded to doubles, k0 added to the table before its one rounding). Its largest error on
 //   |r| <= 2^-7 is 0.2183 ns against the Taylor form's 0.025 ns, so the acceptance margin grows from 1 ns to
@@ -194,9 +194,15 @@ MSIM_HD int32_t interval_ms_fast(uint64_t u, const LogTab *__restrict__ tab, boo
 constexpr int K1_EROWS = 16;
 constexpr int FD_VT_SHIFT = 20 - LOG_BITS - 3;  // vt = vh >> 11: entry index * 8 in bits 3..12, exponent from bit 9
 constexpr uint32_t FD_VT_MIN = ((uint32_t)(1023 - (K1_EROWS - 1)) << 20) >> FD_VT_SHIFT;  // vt of 2^-15
+// One entry of the packed table (below, "the packed form"): everything one fast draw reads, as one 16-byte read.
+struct alignas(16) K1Pair {
+    double invc;  // invc_j * 2^(15 - eps)
+    double A;     // A2[eps, j] less the acceptance margin
+};
 struct K1Log {
     double invc[LOG_TAB];
     double A2[K1_EROWS * LOG_TAB];  // row K1_EROWS - 1 (e = 0) is the general form's A (+ the polynomial's k0)
+    K1Pair P[K1_EROWS * LOG_TAB];   // the packed form's table, entry (eps, j) as A2's
 };
 #if MSIM_FD_DEG4
 constexpr double K1_MARGIN_NS = 1.25;
@@ -218,8 +224,10 @@ constexpr uint32_t K1_OK_RANGE = K1_OK_HI - K1_OK_LO;
 
 // z = (6e11 E + 0.5) / 1e6 by K1's polynomial. FOLD: the table row is chosen by the exponent's low bits (valid
 // only for vt >= FD_VT_MIN); otherwise the general form, for any exponent. vt = (the high word of v) >> 11.
+// On the arrays themselves (K1 keeps only invc and row e = 0 in LDS): A = A2 for FOLD, row e = 0 of it otherwise.
 template <bool FOLD>
-MSIM_HD double k1_interval_z(uint64_t u, const K1Log *__restrict__ tab, uint32_t &vt, FdConsts kc = MSIM_K1_CONSTS)
+MSIM_HD double k1_interval_z_on(uint64_t u, const double *__restrict__ invc, const double *__restrict__ A, uint32_t &vt,
+                                FdConsts kc = MSIM_K1_CONSTS)
 {
     const uint32_t lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
     const double c = __builtin_fma(u32_to_f64(lo >> 11), -0x1.0p-53, 1.0);  // exact
@@ -231,12 +239,12 @@ MSIM_HD double k1_interval_z(uint64_t u, const K1Log *__restrict__ tab, uint32_t
     // compiler cannot merge them into one ds_read2st64_b64 (32-bank: see the table sizes above)
     vt = vh >> FD_VT_SHIFT;
     const uint32_t joff = vt & ((LOG_TAB - 1u) << 3);
-    uint32_t aoff = FOLD ? vt & ((K1_EROWS * LOG_TAB - 1u) << 3) : joff + (K1_EROWS - 1u) * LOG_TAB * 8u;
+    uint32_t aoff = FOLD ? vt & ((K1_EROWS * LOG_TAB - 1u) << 3) : joff;
 #if defined(__HIP_DEVICE_COMPILE__)
     if (!FOLD) asm("" : "+v"(aoff));  // as interval_fast_z: keeps the general form's two reads apart
 #endif
-    const double Aj = *(const double *)((const char *)tab->A2 + aoff);
-    const double r = __builtin_fma(w, *(const double *)((const char *)tab->invc + joff), -1.0);
+    const double Aj = *(const double *)((const char *)A + aoff);
+    const double r = __builtin_fma(w, *(const double *)((const char *)invc + joff), -1.0);
 #if MSIM_FD_DEG4
     double p = __builtin_fma(r, kc.c4, kc.c3);
 #else
@@ -249,13 +257,15 @@ MSIM_HD double k1_interval_z(uint64_t u, const K1Log *__restrict__ tab, uint32_t
     if (FOLD) return z0;
     return __builtin_fma((double)((int)(vt >> (20 - FD_VT_SHIFT)) - 1023), FD_CE, z0);
 }
-// Interval and acceptance key (as interval_ms_fast_key): the reference's value iff key < K1_OK_RANGE and, for
-// FOLD, vt >= FD_VT_MIN.
 template <bool FOLD>
-MSIM_HD int32_t k1_interval_key(uint64_t u, const K1Log *__restrict__ tab, uint32_t &key, uint32_t &vt,
-                                FdConsts kc = MSIM_K1_CONSTS)
+MSIM_HD double k1_interval_z(uint64_t u, const K1Log *__restrict__ tab, uint32_t &vt, FdConsts kc = MSIM_K1_CONSTS)
 {
-    const double z = k1_interval_z<FOLD>(u, tab, vt, kc);
+    return k1_interval_z_on<FOLD>(u, tab->invc, FOLD ? tab->A2 : tab->A2 + (K1_EROWS - 1) * LOG_TAB, vt, kc);
+}
+// Interval and acceptance key of a z (as interval_ms_fast_key): the reference's value iff key < K1_OK_RANGE and,
+// for the folded table, vt >= FD_VT_MIN.
+MSIM_HD int32_t k1_z_key(double z, uint32_t &key)
+{
     const int32_t q = (int32_t)z;  // z >= 0.5e-6 > 0: truncation = floor
 #if defined(__HIP_DEVICE_COMPILE__)
     const double f = __builtin_amdgcn_fract(z);
@@ -263,6 +273,21 @@ MSIM_HD int32_t k1_interval_key(uint64_t u, const K1Log *__restrict__ tab, uint3
     const double f = z - (double)q;
 #endif
     key = (uint32_t)(__builtin_bit_cast(uint64_t, f) >> 32) - K1_OK_LO;
+    return q;
+}
+template <bool FOLD>
+MSIM_HD int32_t k1_interval_key(uint64_t u, const K1Log *__restrict__ tab, uint32_t &key, uint32_t &vt,
+                                FdConsts kc = MSIM_K1_CONSTS)
+{
+    return k1_z_key(k1_interval_z<FOLD>(u, tab, vt, kc), key);
+}
+// The general form on K1's two small arrays (invc and row e = 0 of A2): k1_interval_general's value and flag.
+MSIM_HD int32_t k1_interval_general_on(uint64_t u, const double *__restrict__ invc, const double *__restrict__ A0, bool &ok,
+                                       FdConsts kc = MSIM_K1_CONSTS)
+{
+    uint32_t key, vt;
+    const int32_t q = k1_z_key(k1_interval_z_on<false>(u, invc, A0, vt, kc), key);
+    ok = key < K1_OK_RANGE;
     return q;
 }
 // K1's fast form alone: ok == false sends the draw to the general form.
@@ -278,6 +303,74 @@ MSIM_HD int32_t k1_interval_general(uint64_t u, const K1Log *__restrict__ tab, b
     uint32_t key, vt;
     const int32_t q = k1_interval_key<false>(u, tab, key, vt, kc);
     ok = key < K1_OK_RANGE;
+    return q;
+}
+
+// ---------------------------------------------------------------- the packed form (what K1's quad runs)
+// The folded form above, with the work its result does not need taken out; k1_interval_fast above stays the
+// checked definition the packed form is compared with (tests/native/k1pack_check.cpp).
+//
+// Packing: one 16-byte entry per draw, P[(vh >> 14) & 1023] = {invc_j * 2^(15 - eps), A2[eps, j]}, and
+//   r = fma(v, P.invc, -1) on v itself. With v = w * 2^e and e = eps - 15 in [-15, 0], v * (invc_j * 2^-e) and
+//   w * invc_j are the same real number (the scaling is by a power of two, at most 2^15: no overflow, no
+//   underflow), so the FMA rounds to the same bits as the folded form's: r, z and the interval are identical.
+//   The mantissa's rebuild (v_and, v_or), one of the two address masks and one of the two LDS reads go. For
+//   e < -15 the row aliases as before, and the quad rejects on the smallest high word of its four v's.
+// Folded margin: the entry's A is A2 - M, M = K1_MARGIN_NS * 1e-6 ms (80-bit, rounded once, like every entry), so
+//   the form computes z' = z - M. Let f' = fract(z'). The draw is accepted iff hi(f') < K1P_OK_HI =
+//   hi(1 - 2M), which implies f' < 1 - 2M, and then:
+//     z' >= 0: fract of a negative z' (only z < M; u = 0 is such a draw) is just below 1 on the device and
+//       negative on the host (z' - trunc(z')); both fail the test;
+//     frac(z) = f' + M lies in [M, 1 - M): z is at least the margin away from both millisecond boundaries, the
+//       condition under which floor(z) is the reference's interval (above);
+//     floor(z') = floor(z), since z' = floor(z) + (frac(z) - M) with 0 <= frac(z) - M < 1.
+//   Conversely frac(z) < M gives f' >= 1 - M: rejected. So one upper bound on the raw high word replaces the
+//   two-sided test, the per-draw rebase of the key (v_add_u32) goes, and the quad's max runs on the raw high
+//   words. The lower margin is now M itself (the folded form asks one high-word step more), the upper one
+//   1 - 6 * 2^-21 - M = 1.61 ns; rejected share 2^-15 + 2.86e-6.
+constexpr uint32_t K1P_OK_HI = 0x3FEFFFFAu;  // hi(1 - 2.5e-6) (exclusive)
+constexpr uint32_t K1P_VH_MIN = (uint32_t)(1023 - (K1_EROWS - 1)) << 20;  // high word of 2^-15
+// z - M of the packed form; vh = the high word of v, r = the polynomial's argument.
+MSIM_HD double k1p_interval_z(uint64_t u, const K1Pair *__restrict__ P, uint32_t &vh, double &r, FdConsts kc = MSIM_K1_CONSTS)
+{
+    const uint32_t lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
+    const double c = __builtin_fma(u32_to_f64(lo >> 11), -0x1.0p-53, 1.0);  // exact
+    const double v = __builtin_fma(u32_to_f64(hi), -0x1.0p-32, c);           // exact: 1 - (u>>11) 2^-53
+    vh = (uint32_t)(__builtin_bit_cast(uint64_t, v) >> 32);
+    const uint32_t off = (vh >> (FD_VT_SHIFT + 3 - 4)) & ((K1_EROWS * LOG_TAB - 1u) << 4);
+    const K1Pair en = *(const K1Pair *)((const char *)P + off);
+    r = __builtin_fma(v, en.invc, -1.0);
+#if MSIM_FD_DEG4
+    double p = __builtin_fma(r, kc.c4, kc.c3);
+#else
+    double p = __builtin_fma(r, kc.c5, kc.c4);
+    p = __builtin_fma(r, p, kc.c3);
+#endif
+    p = __builtin_fma(r, p, kc.c2);
+    p = __builtin_fma(r, p, kc.c1);
+    return __builtin_fma(r, p, en.A);
+}
+// Interval and acceptance key: the reference's value iff key < K1P_OK_HI and vh >= K1P_VH_MIN.
+MSIM_HD int32_t k1p_interval_key(uint64_t u, const K1Pair *__restrict__ P, uint32_t &key, uint32_t &vh,
+                                 FdConsts kc = MSIM_K1_CONSTS)
+{
+    double r;
+    const double z = k1p_interval_z(u, P, vh, r, kc);
+    const int32_t q = (int32_t)z;  // an accepted z is >= 0: truncation = floor
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double f = __builtin_amdgcn_fract(z);
+#else
+    const double f = z - (double)q;
+#endif
+    key = (uint32_t)(__builtin_bit_cast(uint64_t, f) >> 32);
+    return q;
+}
+// The packed form alone: ok == false sends the draw to the general form.
+MSIM_HD int32_t k1p_interval_fast(uint64_t u, const K1Pair *__restrict__ P, bool &ok, FdConsts kc = MSIM_K1_CONSTS)
+{
+    uint32_t key, vh;
+    const int32_t q = k1p_interval_key(u, P, key, vh, kc);
+    ok = key < K1P_OK_HI && vh >= K1P_VH_MIN;
     return q;
 }
 
@@ -317,6 +410,23 @@ MSIM_HD uint32_t pick_info(uint64_t u, const PickTab *__restrict__ tab)
     return tab->info[q];
 }
 
+// K1's picker draw: the fast pick reads only the high word h of the draw, so the output step
+// rotl(s0 + s1, 17) + s0 is formed in its high half alone: the 64-bit sum, the high half of the rotate, and a
+// 32-bit add that leaves out the carry of the low halves. The state update is rng_next's. The result h' has
+// h = h' or h' + 1 (mod 2^32). With 100 h' = p 2^32 + key and key < PICK_HI_RARE_LO = 2^32 - 256:
+// 100 (h' + 1) = p 2^32 + key + 100 with key + 100 < 2^32 - 156, so h' + 1 has the same p and its low word is
+// below PICK_RARE_LO: q = p for either carry. (h' = 2^32 - 1, whose successor wraps, has key = 2^32 - 100: rare.)
+// A key at or above the band (6e-8 of draws) sends the quad to pick_q_exact on the full rng_next, as before.
+constexpr uint32_t PICK_HI_RARE_LO = 0xFFFFFF00u;  // low word of 100 h' at or above it: the exact path
+MSIM_HD uint32_t rng_next_hi(Rng &r)
+{
+    const uint32_t h = (uint32_t)(rotl64(r.s0 + r.s1, 17) >> 32) + (uint32_t)(r.s0 >> 32);
+    (void)rng_next(r);  // the state update; its own output step is unused and compiles away
+    return h;
+}
+// p = floor(100 h / 2^32) and its key (the low word of 100 h): pick_q_fast_key on a high word.
+MSIM_HD uint32_t pick_p_key(uint32_t h, uint32_t &key) { return pick_q_fast_key((uint64_t)h << 32, key); }
+
 // ---------------------------------------------------------------- host table builders
 inline void build_log_table(LogTab *out)
 {
@@ -337,7 +447,12 @@ inline void build_k1_log(K1Log *out)
         const double invc = 1.0 / (1.0 + (j + 0.5) / LOG_TAB);  // the same invc as build_log_table
         out->invc[j] = invc;
         const long double a = (0.5L - 6e11L * -logl((long double)invc)) * 1e-6L + FD4_K0;
-        for (int eps = 0; eps < K1_EROWS; ++eps) out->A2[eps * LOG_TAB + j] = (double)(a + (eps - (K1_EROWS - 1)) * ce);
+        for (int eps = 0; eps < K1_EROWS; ++eps) {
+            const long double ae = a + (eps - (K1_EROWS - 1)) * ce;
+            out->A2[eps * LOG_TAB + j] = (double)ae;
+            // the packed form's entry: invc scaled by 2^-e (exact), A less the acceptance margin
+            out->P[eps * LOG_TAB + j] = K1Pair{ldexp(invc, K1_EROWS - 1 - eps), (double)(ae - (long double)K1_MARGIN_NS * 1e-6L)};
+        }
     }
 }
 

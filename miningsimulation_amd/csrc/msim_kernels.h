@@ -77,6 +77,8 @@ void k1_tables_build(const uint64_t *perc, const int64_t *prop, const uint8_t *s
 bool k1_tables_uniform(const int64_t *prop, const uint8_t *selfish, int m, uint32_t *fthr);
 void k1_log_build(K1Log *log);
 hipError_t launch_picks(const PickTab *pt, const uint64_t *u, int32_t *out, uint64_t n, hipStream_t s);
+// K1's quad of draws (fast form, then its redraw when flagged) from n given pairs of stream states (test surface).
+hipError_t launch_k1_quads(const PipeTables &t, const Rng *st, uint32_t *out, uint64_t n, hipStream_t s);
 constexpr int TPB = 256;  // 4 waves of 64 lanes per workgroup
 size_t partials_words(uint32_t m, uint32_t n, uint32_t err_cap);
 

@@ -308,45 +308,48 @@ MSIM_HD void draw_quad_exact(Rng ri, Rng rp, const LogTab *__restrict__ lt, cons
     }
 }
 
-// K1's own forms of the same draws (msim_fastdraw.h, "K1's form"): any 64-bit draw still gets the reference's
-// interval and finder.
-MSIM_HD uint32_t k1_draw_interval(Rng &ri, const K1Log *__restrict__ kl, FdConsts kc)
+// K1's own forms of the same draws (msim_fastdraw.h, "K1's form" and "the packed form"): any 64-bit draw still gets
+// the reference's interval and finder. Of K1Log the lane body reads the packed table P (the quad) and, for the
+// redraw by the general form, invc and row e = 0 of A2 (A0): K1 keeps only those in LDS.
+MSIM_HD uint32_t k1_draw_interval(Rng &ri, const double *__restrict__ invc, const double *__restrict__ A0, FdConsts kc)
 {
     const uint64_t u = rng_next(ri);
     bool ok;
-    const int32_t q = k1_interval_general(u, kl, ok, kc);
+    const int32_t q = k1_interval_general_on(u, invc, A0, ok, kc);
 #if defined(__HIP_DEVICE_COMPILE__)
     return (uint32_t)(ok ? q : interval_ms_exact_dev(u));
 #else
     return (uint32_t)(ok ? q : (int32_t)interval_ms_of(u));
 #endif
 }
-// As draw_quad_fast. The exponent limit of the folded table is checked once per quad: the smallest high word
-// of the four v's (shifted: vt) against FD_VT_MIN.
-MSIM_HD bool k1_quad_fast(Rng &ri, Rng &rp, const K1Log *__restrict__ kl, const PickTab *__restrict__ kp, FdConsts kc,
-                          uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB])
+// As draw_quad_fast, on the packed form and the high-word picker. The exponent limit of the folded table is
+// checked once per quad: the smallest high word of the four v's against K1P_VH_MIN.
+MSIM_HD bool k1p_quad_fast(Rng &ri, Rng &rp, const K1Pair *__restrict__ P, const PickTab *__restrict__ kp, FdConsts kc,
+                           uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB])
 {
     uint32_t ki = 0, kk = 0, vmin = 0xFFFFFFFFu;
 #pragma unroll
     for (int q = 0; q < K1_QB; ++q) {
-        const uint64_t ui = rng_next(ri), up = rng_next(rp);
-        uint32_t a, b, vt;
-        I[q] = (uint32_t)k1_interval_key<MSIM_FD_A2 != 0>(ui, kl, a, vt, kc);
-        info[q] = kp->info[pick_q_fast_key(up, b)];
+        const uint64_t ui = rng_next(ri);
+        const uint32_t hp = rng_next_hi(rp);
+        uint32_t a, b, vh;
+        I[q] = (uint32_t)k1p_interval_key(ui, P, a, vh, kc);
+        info[q] = kp->info[pick_p_key(hp, b)];
         ki = a > ki ? a : ki;
         kk = b > kk ? b : kk;
-        vmin = vt < vmin ? vt : vmin;
+        vmin = vh < vmin ? vh : vmin;
     }
-    return ki >= K1_OK_RANGE || kk >= PICK_RARE_LO || (MSIM_FD_A2 && vmin < FD_VT_MIN);
+    return ki >= K1P_OK_HI || kk >= PICK_HI_RARE_LO || vmin < K1P_VH_MIN;
 }
 // The redraw of a flagged quad: every interval by the general form first (3e-5 of draws only left the folded
-// table's exponent range), glibc's sequence for the one within the margin of a millisecond boundary.
-MSIM_HD void k1_quad_exact(Rng ri, Rng rp, const K1Log *__restrict__ kl, const PickTab *__restrict__ kp, FdConsts kc,
-                           uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB])
+// table's exponent range), glibc's sequence for the one within the margin of a millisecond boundary; every pick
+// exactly, on the full draw.
+MSIM_HD void k1_quad_exact(Rng ri, Rng rp, const double *__restrict__ invc, const double *__restrict__ A0,
+                           const PickTab *__restrict__ kp, FdConsts kc, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB])
 {
 #pragma unroll
     for (int q = 0; q < K1_QB; ++q) {
-        I[q] = k1_draw_interval(ri, kl, kc);
+        I[q] = k1_draw_interval(ri, invc, A0, kc);
         info[q] = kp->info[pick_q_exact(rng_next(rp))];
     }
 }
@@ -359,12 +362,11 @@ struct GeneralDraws {
     const PickTab *pt;
     FdConsts kc;
     MSIM_HD void begin() { kc = fd_consts(); }
-    MSIM_HD FdConsts quad_consts() const { return kc; }
     MSIM_HD uint32_t interval(Rng &ri) const { return draw_interval(ri, lt, kc); }
     MSIM_HD uint32_t pick(Rng &rp) const { return pick_info(rng_next(rp), pt); }
-    MSIM_HD bool quad_fast(Rng &ri, Rng &rp, FdConsts kq, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
+    MSIM_HD bool quad_fast(Rng &ri, Rng &rp, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
     {
-        return draw_quad_fast(ri, rp, lt, pt, kq, I, info);
+        return draw_quad_fast(ri, rp, lt, pt, kc, I, info);
     }
     MSIM_HD void quad_exact(const Rng &ri, const Rng &rp, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
     {
@@ -376,7 +378,8 @@ struct GeneralDraws {
 // K1Draws: K1's tables. UNI (k1_uniform_fthr): one scalar fast threshold, and the pick entry IS the row offset.
 template <bool UNI>
 struct K1Draws {
-    const K1Log *kl;
+    const K1Pair *P;                // K1Log's packed table
+    const double *invc, *A0;        // K1Log's invc and row e = 0 of A2 (the general-form redraw)
     const PickTab *kp;  // build_k1_pick(uni = UNI)
     uint32_t fthr;      // UNI: every finder's fast threshold
     FdConsts kc;
@@ -384,36 +387,26 @@ struct K1Draws {
     {
         kc = MSIM_K1_CONSTS;
 #if defined(__HIP_DEVICE_COMPILE__)
-        // all coefficients in SGPRs; the leading one reaches a VGPR per quad (quad_consts)
+        // every addend in an SGPR; the leading coefficient, a multiplicand beside the SGPR addend (one VOP3 reads
+        // at most one SGPR), in a VGPR pair held across the loop: at 4 waves per SIMD the budget has room for it
         asm("" : "+s"(kc.c1));
         asm("" : "+s"(kc.c2));
         asm("" : "+s"(kc.c3));
-        asm("" : "+s"(kc.c4));
 #if !MSIM_FD_DEG4
-        asm("" : "+s"(kc.c5));
+        asm("" : "+s"(kc.c4));
 #endif
+        asm volatile("" : "+v"(kc.MSIM_K1_LEAD));
 #endif
     }
-    MSIM_HD FdConsts quad_consts() const
-    {
-        FdConsts kq = kc;
-#if defined(__HIP_DEVICE_COMPILE__)
-        // the polynomial's leading coefficient, a VGPR operand (one VOP3 reads at most one SGPR), copied from
-        // its SGPR each quad (one v_mov_b64) instead of being held across the loop, where the register budget
-        // of K1 sent it to scratch
-        asm volatile("v_mov_b64 %0, %1" : "=v"(kq.MSIM_K1_LEAD) : "s"(kc.MSIM_K1_LEAD));
-#endif
-        return kq;
-    }
-    MSIM_HD uint32_t interval(Rng &ri) const { return k1_draw_interval(ri, kl, kc); }
+    MSIM_HD uint32_t interval(Rng &ri) const { return k1_draw_interval(ri, invc, A0, kc); }
     MSIM_HD uint32_t pick(Rng &rp) const { return kp->info[pick_q_exact(rng_next(rp))]; }
-    MSIM_HD bool quad_fast(Rng &ri, Rng &rp, FdConsts kq, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
+    MSIM_HD bool quad_fast(Rng &ri, Rng &rp, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
     {
-        return k1_quad_fast(ri, rp, kl, kp, kq, I, info);
+        return k1p_quad_fast(ri, rp, P, kp, kc, I, info);
     }
     MSIM_HD void quad_exact(const Rng &ri, const Rng &rp, uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB]) const
     {
-        k1_quad_exact(ri, rp, kl, kp, kc, I, info);
+        k1_quad_exact(ri, rp, invc, A0, kp, kc, I, info);
     }
     MSIM_HD bool slow(uint32_t next, uint32_t info) const { return next <= (UNI ? fthr : info_fthr(info)); }
     MSIM_HD uint32_t row(uint32_t info) const { return UNI ? info : info & (15u << INFO_K_SHIFT); }
@@ -430,7 +423,6 @@ struct K1Draws {
 //                                     block after the next one: the consumer steps them, not the wave)
 //   group(g, sum, end)                band only: sum of the group's intervals, and the time from the segment's
 //                                     start to the group's end
-//   quad()                            start of a quad of blocks
 //   group_start(g, w0, ri, rp)        band only: before group g's first block (its word and the streams
 //                                     after it; snapshot the counters)
 // Blocks are drawn four at a time (draw_quad_fast); the streams after a block inside a quad, needed only
@@ -448,15 +440,13 @@ MSIM_HD uint64_t draw_segment_with(Ctx &cx, Draws &d, Rng &ri, Rng &rp, uint32_t
         uint32_t gacc = 0;
         for (uint32_t q4 = 0; q4 < GROUP / K1_QB; ++q4) {
             uint32_t I[K1_QB], info[K1_QB];
-            cx.quad();  // per-quad values the context rebuilds rather than holding across the loop
-            const FdConsts kq = d.quad_consts();
             // The quad's start states are read only on the two rare paths below; at a register budget of 96 VGPRs
             // or fewer (5 or more waves per SIMD, msim_drawgen.hip) the compiler keeps them in scratch, written
             // once per quad; at the shipped 4 waves they stay in registers. Measured on MI355X: recovering them by
             // inverse stepping instead (no scratch, 84 VGPRs) made K1 11 % slower at the same occupancy
             // (profiles/r03/INDEX.md, k1 A/B).
             const Rng ri0 = ri, rp0 = rp;
-            if (d.quad_fast(ri, rp, kq, I, info)) d.quad_exact(ri0, rp0, I, info);
+            if (d.quad_fast(ri, rp, I, info)) d.quad_exact(ri0, rp0, I, info);
 #pragma unroll
             for (int q = 0; q < K1_QB; ++q) {
                 gacc += Icur;
@@ -487,7 +477,16 @@ template <bool UNI, class Ctx>
 MSIM_HD uint64_t draw_segment_k1(Ctx &cx, Rng &ri, Rng &rp, const K1Log *__restrict__ kl,
                                  const PickTab *__restrict__ kp, uint32_t fthr, uint32_t b0, uint32_t seg, bool band)
 {
-    K1Draws<UNI> d{kl, kp, fthr, MSIM_K1_CONSTS};
+    K1Draws<UNI> d{kl->P, kl->invc, kl->A2 + (K1_EROWS - 1) * LOG_TAB, kp, fthr, MSIM_K1_CONSTS};
+    return draw_segment_with(cx, d, ri, rp, b0, seg, band);
+}
+// The same on the three arrays of K1Log the lane body reads (K1 holds only these in LDS).
+template <bool UNI, class Ctx>
+MSIM_HD uint64_t draw_segment_k1_on(Ctx &cx, Rng &ri, Rng &rp, const K1Pair *__restrict__ P, const double *__restrict__ invc,
+                                    const double *__restrict__ A0, const PickTab *__restrict__ kp, uint32_t fthr, uint32_t b0,
+                                    uint32_t seg, bool band)
+{
+    K1Draws<UNI> d{P, invc, A0, kp, fthr, MSIM_K1_CONSTS};
     return draw_segment_with(cx, d, ri, rp, b0, seg, band);
 }
 
