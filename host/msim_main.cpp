@@ -12,7 +12,7 @@
 //   msim_main [n_gpus] [seed_base] [default|c5]
 //   msim_main --grid H1,H2,..:P1,P2,.. [--runs R] [--gpus N] [--seed S] [--json]
 //        SetupMiners with miner 0 selfish at H% (miner 1 at 59-H%) and every propagation P ms
-//   msim_main --sweep FILE.json [--runs R] [--gpus N] [--seed S] [--json] [--contrast P]
+//   msim_main --sweep FILE.json [--runs R] [--gpus N] [--seed S] [--json] [--contrast P] [--shared-draws]
 //        {"runs": R, "seed_base": S, "duration_ms": D, "total_weight": W,
 //         "grid": {"selfish_perc": [..], "propagation_ms": [..]}}            or
 //         "points": [{"miners": [{"id": 0, "perc": 40, "propagation_ms": 1000, "selfish": true}, ..]}, ..]}
@@ -256,6 +256,7 @@ struct SweepSpec {
     bool json = false;
     bool errors = false;
     long long contrast = -1;  // --contrast P: the baseline point, or -1
+    bool shared_draws = false;  // --shared-draws: msim_sweep_create_ex(MSIM_SWEEP_SHARED_DRAWS)
 };
 
 static void AddGrid(SweepSpec &sp, const std::vector<int64_t> &hs, const std::vector<int64_t> &props)
@@ -311,7 +312,7 @@ static int RunSweep(const SweepSpec &sp)
         cfgs.push_back(c);
     }
     msim_sweep *sw = nullptr;
-    if (rc == MSIM_OK) rc = msim_sweep_create(cfgs.data(), (uint32_t)cfgs.size(), &sw);
+    if (rc == MSIM_OK) rc = msim_sweep_create_ex(cfgs.data(), (uint32_t)cfgs.size(), sp.shared_draws ? MSIM_SWEEP_SHARED_DRAWS : 0u, &sw);
     const uint32_t m = cfgs.empty() ? 0 : msim_config_miner_count(cfgs[0]);
     std::vector<msim_stats> st(sp.points.size() * m);
     std::vector<msim_errors> errs;
@@ -400,6 +401,7 @@ int main(int argc, char **argv)
             for (int i = 3; i < argc; ++i) {
                 const std::string a = argv[i];
                 if (a == "--json") sp.json = true;
+                else if (a == "--shared-draws") sp.shared_draws = true;
                 else if (a == "--runs" && i + 1 < argc) sp.runs = std::stoull(argv[++i]);
                 else if (a == "--gpus" && i + 1 < argc) sp.gpus = std::stoi(argv[++i]);
                 else if (a == "--seed" && i + 1 < argc) sp.seed_base = (uint32_t)std::stoul(argv[++i]);

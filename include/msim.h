@@ -192,6 +192,37 @@ int msim_device_picks(const msim_config *cfg, const uint64_t *d_uniform, int32_t
  *   sums[p * M + k], per_run[(p * runs_per_point + r) * M + k], best_height[p * runs_per_point + r]. */
 typedef struct msim_sweep msim_sweep;
 int msim_sweep_create(const msim_config *const *cfgs, uint32_t n_points, msim_sweep **out);
+/* msim_sweep_create with flags (0: exactly msim_sweep_create; unknown bits: MSIM_E_INVALID).
+ * MSIM_SWEEP_SHARED_DRAWS: the shared-draw form of honest sweeps. The reference compares propagation delays by
+ * editing SetupMiners and rebuilding once per point (README.md:21-27: the same hashrates at 10 s and at 100 ms).
+ * Points of a sweep with the same weights and duration see the same seeds and so the same draws; only which blocks
+ * start a fork episode depends on the delays. Such points form a draw group: the draw kernel runs ONCE per group
+ * (on the group's envelope network: every miner at its largest delay over the group), a split kernel derives each
+ * point's own episode list from the envelope's, and the episode and combine kernels run per point. Results are those
+ * of msim_sweep_create, bit for bit. The flag takes effect only when the event-skipping pipeline takes every point
+ * (honest, at most MSIM_MAX_MINERS miners with percentages, delays below 262 s, rare forks; MSIM_NO_PIPELINE unset at
+ * config creation); any other sweep runs exactly as without it. A group whose envelope the pipeline does not take is
+ * split (its point with the largest delay leaves it) until it does.
+ * A test switch, MSIM_SWEEP_SHARED_MAX_GROUP=<n> (0 < n < 8), read at every launch: a split pass serves at most n
+ * points of a group, so a group of five takes the further split passes (never further draw passes) that otherwise
+ * begin past 8 points. */
+#define MSIM_SWEEP_SHARED_DRAWS 1u
+int msim_sweep_create_ex(const msim_config *const *cfgs, uint32_t n_points, uint32_t flags, msim_sweep **out);
+/* Host only, no device: the draw group of a point (0 .. draw_groups - 1), or -1 when the sweep does not run in the
+ * shared-draw form (flags 0, or a sweep the flag has no effect on) or the point does not exist. (The reference has
+ * one network per build, README.md:21-27; no counterpart.) */
+int msim_sweep_group_of(const msim_sweep *sweep, uint32_t point);
+/* How msim_sweep_launch will execute runs_per_point runs of every point, as msim_pipeline_info for a config (the
+ * reference: one rebuild per point, README.md:21-27). */
+typedef struct msim_sweep_plan {
+    uint32_t engine;          /* 0: per-lane kernel, one lane per (point, run); 1: shared-draw pipeline; 3: entity
+                                 engine (a point with selfish miners); 4: general engine */
+    uint32_t draw_groups;     /* engine 1: draw passes per slice; else 0 */
+    uint32_t largest_group;   /* engine 1: points of the largest draw group; else 0 */
+    uint32_t slice_runs;      /* runs per point and slice (engine 1: of the group with the smallest slices) */
+    uint64_t workspace_bytes; /* msim_sweep_workspace_bytes */
+} msim_sweep_plan;
+int msim_sweep_info(const msim_sweep *sweep, uint64_t runs_per_point, msim_sweep_plan *out);
 void msim_sweep_destroy(msim_sweep *sweep);
 size_t msim_sweep_workspace_bytes(const msim_sweep *sweep, uint64_t runs_per_point);
 /* Device-resident, asynchronous on `stream`; d_sums: n_points * M msim_sums; d_status as msim_launch. */

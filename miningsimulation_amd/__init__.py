@@ -23,6 +23,7 @@ from .simulation import (  # noqa: F401
     c4_grid,
     c5_network,
     exact_stats_total,
+    propagation_sweep,
     report,
     sample_intervals,
     sample_picks,

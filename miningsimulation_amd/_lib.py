@@ -51,6 +51,9 @@ EXPORTED = (
     "msim_timing_read_all",
     "msim_pipeline_info",
     "msim_sweep_create",
+    "msim_sweep_create_ex",
+    "msim_sweep_group_of",
+    "msim_sweep_info",
     "msim_sweep_destroy",
     "msim_sweep_workspace_bytes",
     "msim_sweep_launch",
@@ -115,6 +118,19 @@ class MsimPipelineLayout(ctypes.Structure):
         ("workspace_bytes", ctypes.c_uint64),
         ("rho", ctypes.c_double),
     ]
+
+
+class MsimSweepPlan(ctypes.Structure):
+    _fields_ = [
+        ("engine", ctypes.c_uint32),
+        ("draw_groups", ctypes.c_uint32),
+        ("largest_group", ctypes.c_uint32),
+        ("slice_runs", ctypes.c_uint32),
+        ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
+MSIM_SWEEP_SHARED_DRAWS = 1
 
 
 class MsimError(RuntimeError):
@@ -229,6 +245,12 @@ def _load() -> ctypes.CDLL:
     lib.msim_pipeline_info.restype = ctypes.c_int
     lib.msim_sweep_create.argtypes = [ctypes.POINTER(vp), u32, ctypes.POINTER(vp)]
     lib.msim_sweep_create.restype = ctypes.c_int
+    lib.msim_sweep_create_ex.argtypes = [ctypes.POINTER(vp), u32, u32, ctypes.POINTER(vp)]
+    lib.msim_sweep_create_ex.restype = ctypes.c_int
+    lib.msim_sweep_group_of.argtypes = [vp, u32]
+    lib.msim_sweep_group_of.restype = ctypes.c_int
+    lib.msim_sweep_info.argtypes = [vp, u64, ctypes.POINTER(MsimSweepPlan)]
+    lib.msim_sweep_info.restype = ctypes.c_int
     lib.msim_sweep_destroy.argtypes = [vp]
     lib.msim_sweep_destroy.restype = None
     lib.msim_sweep_workspace_bytes.argtypes = [vp, u64]

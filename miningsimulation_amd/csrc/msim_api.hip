@@ -48,6 +48,7 @@ enum TableKey : uint64_t {
     TAB_SEL = 2ull << 32,       // SelParams of every point + point lists
     TAB_GEN = 3ull << 32,       // GenParams of every point + arrays
     TAB_POINTS = 4ull << 32,    // SimParams[n_points]
+    TAB_SPLIT = 5ull << 32,     // shared-draw sweeps: the points' split thresholds, [16] each, in draw-group order
 };
 
 // A network as the general engine reads it (msim_general.h): integer weights summing to W.
@@ -134,6 +135,22 @@ struct msim_sweep {
     bool general = false;
     bool gen_full = false;  // some point needs G's full last window tier (gen_needs_full)
     std::vector<GenHost> gens;
+    // The shared-draw form (msim_sweep_create_ex with MSIM_SWEEP_SHARED_DRAWS, every point on the honest pipeline;
+    // msim_sweepsplit.h): the points partitioned into draw groups by (weights, duration), each with the config of
+    // its envelope network (the group's weights, every miner at its largest delay over the group's points), which
+    // supplies rho, the layout and the device tables of the group's one draw pass.
+    bool shared = false;
+    struct DrawGroup {
+        std::vector<uint32_t> points;
+        msim_config *env = nullptr;
+    };
+    std::vector<DrawGroup> dgroups;
+    std::vector<int32_t> group_of;  // per point
+    std::vector<double> rhos;       // per point (its capacities and its K2 kind follow its own rho)
+    ~msim_sweep()
+    {
+        for (auto &g : dgroups) delete g.env;
+    }
 };
 
 namespace {
@@ -845,6 +862,295 @@ int launch_wide_cfg(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs,
     return MSIM_OK;
 }
 
+
+// ---------------------------------------------------------------- shared-draw sweeps (msim_sweepsplit.h)
+// Draw groups of an eligible sweep: points with the same weights and duration share a group; a group whose envelope
+// network the pipeline does not take (heterogeneous points can push its rho past PIPE_MAX_RHO) loses its point with
+// the largest delay to a group of its own until it does. A group of one is the plain pipeline on that point.
+int build_draw_groups(msim_sweep *w, const msim_config *const *cfgs, uint32_t np)
+{
+    std::vector<std::vector<uint32_t>> work;
+    for (uint32_t i = 0; i < np; ++i) {
+        bool placed = false;
+        for (auto &g : work) {
+            const msim_config *f = cfgs[g[0]];
+            if (f->p.duration_ms == cfgs[i]->p.duration_ms && !memcmp(f->perc, cfgs[i]->perc, sizeof(uint64_t) * f->n)) {
+                g.push_back(i);
+                placed = true;
+                break;
+            }
+        }
+        if (!placed) work.push_back({i});
+    }
+    auto max_prop = [&](uint32_t i) {
+        int64_t v = 0;
+        for (uint32_t k = 0; k < cfgs[i]->n; ++k) v = cfgs[i]->prop[k] > v ? cfgs[i]->prop[k] : v;
+        return v;
+    };
+    w->group_of.assign(np, -1);
+    for (size_t g = 0; g < work.size(); ++g) {  // `work` grows while groups are split
+        for (;;) {
+            const msim_config *f = cfgs[work[g][0]];
+            std::vector<msim_miner> ms(f->n);
+            for (uint32_t k = 0; k < f->n; ++k) {
+                int64_t pe = 0;
+                for (uint32_t i : work[g]) pe = cfgs[i]->prop[k] > pe ? cfgs[i]->prop[k] : pe;
+                ms[k] = msim_miner{f->ids[k], f->perc[k], pe, 0};
+            }
+            msim_config *env = nullptr;
+            const int rc = config_create_impl(ms.data(), f->n, f->p.duration_ms, 100u, &env);
+            if (rc) return rc;
+            if (env->pipe_ok || work[g].size() == 1) {
+                w->dgroups.push_back({work[g], env});
+                break;
+            }
+            delete env;
+            size_t worst = 0;
+            for (size_t j = 1; j < work[g].size(); ++j)
+                if (max_prop(work[g][j]) > max_prop(work[g][worst])) worst = j;
+            const uint32_t pt = work[g][worst];
+            work[g].erase(work[g].begin() + (long)worst);
+            work.push_back({pt});
+        }
+        for (uint32_t i : work[g]) w->group_of[i] = (int32_t)g;
+    }
+    for (uint32_t i = 0; i < np; ++i) w->rhos.push_back(cfgs[i]->rho);
+    w->shared = true;
+    return MSIM_OK;
+}
+
+// Points per split pass: SPLIT_MAX_POINTS, or fewer under the test switch MSIM_SWEEP_SHARED_MAX_GROUP (msim.h).
+uint32_t split_bound()
+{
+    const char *e = getenv("MSIM_SWEEP_SHARED_MAX_GROUP");
+    const long v = e ? atol(e) : 0;
+    return v > 0 && v < (long)msim::SPLIT_MAX_POINTS ? (uint32_t)v : msim::SPLIT_MAX_POINTS;
+}
+
+// Workspace of a shared-draw sweep. Head: the points' counters and status words, then per point the partial sums
+// and the retry list of a single network's launch (ws_layout). Then ONE group region, reused by the groups in turn:
+// the envelope's pipeline layout, the points' list counts (right behind the envelope's: one memset clears them all),
+// and per point nslow_p, slots_p, sel_p and recs_p at the point's own capacities.
+struct SharedGroupLayout {
+    msim::PipeLayout env;
+    std::vector<msim::PipeLayout> pl;  // per point: cap, lcap, k2_kind, rec_words at its own rho (same nr, seg, nseg)
+    std::vector<size_t> nslow_off, slots_off, sel_off, recs_off;
+    size_t counts_off, total;
+};
+struct SharedLayout {
+    size_t counts_off, status_off, point_off, point_bytes, list_off, group_off, total;
+    uint32_t err_cap, slice_runs, largest;
+    std::vector<SharedGroupLayout> g;
+};
+
+SharedGroupLayout shared_group_nr(const msim_sweep *sw, const msim_sweep::DrawGroup &dg, uint32_t nr, uint32_t slots)
+{
+    SharedGroupLayout L;
+    const int64_t D = dg.env->p.duration_ms;
+    L.env = msim::pipe_layout_nr(dg.env->rho, sw->m, D, nr, slots);
+    size_t o = L.env.total;
+    L.counts_off = o;
+    o = align256(o + 4 * dg.points.size());
+    for (uint32_t pt : dg.points) {
+        const msim::PipeLayout P = msim::pipe_layout_nr(sw->rhos[pt], sw->m, D, nr, slots);
+        L.pl.push_back(P);
+        L.nslow_off.push_back(o);
+        o = align256(o + (size_t)P.nseg * nr * 4);
+        L.slots_off.push_back(o);
+        o = align256(o + (size_t)P.nseg * P.cap * nr * 4);
+        L.sel_off.push_back(o);
+        o = align256(o + (size_t)P.lcap * 4);
+        L.recs_off.push_back(o);
+        o = align256(o + (size_t)P.lcap * P.rec_words * 4);
+    }
+    L.total = o;
+    return L;
+}
+
+// The largest slice of the group (all runs, or fewer) that fits the slice budget, as pipe_layout_for; at most
+// MSIM_MAX_SLICE_RUNS runs when that switch is set, as pipe_layout.
+SharedGroupLayout shared_group_layout(const msim_sweep *sw, const msim_sweep::DrawGroup &dg, uint64_t rpp)
+{
+    uint32_t slots = draw_slots() * 3u;
+    if (slots < 1u) slots = 1u;
+    uint64_t nr = (rpp + 255) / 256 * 256;
+    const uint32_t cap = max_slice_runs();
+    if (cap && nr > cap) nr = cap;
+    for (;;) {
+        SharedGroupLayout L = shared_group_nr(sw, dg, (uint32_t)nr, slots);
+        if ((double)L.total <= PIPE_SLICE_BUDGET || nr <= 256) return L;
+        uint64_t next = (uint64_t)((double)nr * PIPE_SLICE_BUDGET / (double)L.total * 0.98) / 256 * 256;
+        if (next >= nr) next = nr - 256;
+        nr = next < 256 ? 256 : next;
+    }
+}
+
+SharedLayout shared_layout(const msim_sweep *sw, uint64_t rpp)
+{
+    SharedLayout l;
+    const uint32_t np = (uint32_t)sw->pts.size();
+    l.err_cap = err_cap_for(rpp);
+    l.counts_off = 0;
+    l.status_off = align256((size_t)np * 8);
+    l.point_off = l.status_off + align256((size_t)np * 8);
+    l.list_off = align256(msim::partials_words(sw->m, (uint32_t)rpp, l.err_cap) * sizeof(uint64_t));
+    l.point_bytes = l.list_off + align256((size_t)l.err_cap * 4);
+    l.group_off = l.point_off + (size_t)np * l.point_bytes;
+    size_t gmax = 0;
+    l.slice_runs = 0;
+    l.largest = 0;
+    for (const auto &dg : sw->dgroups) {
+        l.g.push_back(shared_group_layout(sw, dg, rpp));
+        const SharedGroupLayout &G = l.g.back();
+        gmax = G.total > gmax ? G.total : gmax;
+        l.slice_runs = l.slice_runs == 0 || G.env.nr < l.slice_runs ? G.env.nr : l.slice_runs;
+        l.largest = dg.points.size() > l.largest ? (uint32_t)dg.points.size() : l.largest;
+    }
+    l.total = l.group_off + gmax;
+    return l;
+}
+
+// The launch: per group and slice one K1 on the envelope's tables, S1 in passes of split_bound() points, then K2
+// and K3 per point; per point after its last slice the retry kernel and the finalize; the status words added up.
+int shared_launch_impl(msim_sweep *sw, uint64_t run_begin, uint64_t rpp, uint32_t seed_base, void *d_sums,
+                       void *d_per_run, void *d_best_height, void *d_status, char *ws, size_t workspace_bytes, hipStream_t s)
+{
+    using namespace msim;
+    const uint32_t np = (uint32_t)sw->pts.size(), m = sw->m;
+    const SharedLayout l = shared_layout(sw, rpp);
+    if (workspace_bytes < l.total) return MSIM_E_INVALID;
+    // every table first: the rest of the call allocates nothing and does not synchronise
+    std::vector<PipeTables> tabs(sw->dgroups.size());
+    for (size_t g = 0; g < sw->dgroups.size(); ++g) {
+        const int rc = device_tables(sw->dgroups[g].env, l.g[g].env.seg, l.g[g].env.nseg, &tabs[g]);
+        if (rc) return rc;
+    }
+    const uint32_t *fthr = (const uint32_t *)sw->tables.get(TAB_SPLIT, (size_t)np * 64, [&](char *h, const char *) {
+        uint32_t(*f)[16] = (uint32_t(*)[16])h;
+        for (const auto &dg : sw->dgroups)
+            for (uint32_t pt : dg.points) split_thresholds(sw->pts[pt].prop, m, *f++);
+    });
+    if (!fthr) return MSIM_E_HIP;
+    if (hipMemsetAsync(ws + l.counts_off, 0, (size_t)np * 8, s) != hipSuccess) return MSIM_E_HIP;
+    const uint32_t bound = split_bound();
+    uint32_t first = 0;  // position of the group's first point in draw-group order (the threshold table's)
+    for (size_t g = 0; g < sw->dgroups.size(); ++g) {
+        const msim_sweep::DrawGroup &dg = sw->dgroups[g];
+        const SharedGroupLayout &G = l.g[g];
+        const PipeLayout &L = G.env;
+        const uint32_t ng = (uint32_t)dg.points.size();
+        char *gw = ws + l.group_off;
+        DrawArgs da;
+        da.tab = tabs[g];
+        da.seed_base = seed_base;
+        da.nr = L.nr;
+        da.seg = L.seg;
+        da.gps = L.gps;
+        da.nseg = L.nseg;
+        da.cap = L.cap;
+        da.band_lo = L.band_lo;
+        da.lcap = L.lcap;
+        da.lchunk = L.lchunk;
+        da.segsum = (uint64_t *)(gw + L.segsum_off);
+        da.segcnt = (uint32_t *)(gw + L.segcnt_off);
+        da.nslow = (uint32_t *)(gw + L.nslow_off);
+        da.slots = (uint32_t *)(gw + L.slots_off);
+        da.gsum = (uint32_t *)(gw + L.gsum_off);
+        da.gend = (uint64_t *)(gw + L.gend_off);
+        da.gcum = (uint32_t *)(gw + L.gcum_off);
+        da.grec = (GroupRec *)(gw + L.grec_off);
+        da.list = (EpEntry *)(gw + L.list_off);
+        da.list_count = (uint32_t *)(gw + L.count_off);
+        std::vector<LaunchArgs> las(ng);
+        std::vector<PipeArgs> pas(ng);
+        std::vector<uint32_t *> sels(ng);  // sel_p
+        for (uint32_t i = 0; i < ng; ++i) {
+            const uint32_t pt = dg.points[i];
+            const PipeLayout &P = G.pl[i];
+            char *pw = ws + l.point_off + (size_t)pt * l.point_bytes;
+            uint32_t *counts = (uint32_t *)(ws + l.counts_off) + 2 * pt;
+            LaunchArgs &a = las[i];
+            a.p = sw->pts[pt];
+            a.run_begin = run_begin;
+            a.n = (uint32_t)rpp;
+            a.seed_base = seed_base;
+            a.partials = (uint64_t *)pw;
+            a.sums = (uint64_t *)d_sums + (size_t)pt * 6 * m;
+            a.records = d_per_run ? (uint32_t *)d_per_run + (size_t)pt * rpp * m * 2 : nullptr;
+            a.best_h = d_best_height ? (uint32_t *)d_best_height + (size_t)pt * rpp : nullptr;
+            a.err_count = counts;
+            a.fail_count = counts + 1;
+            a.err_list = (uint32_t *)(pw + l.list_off);
+            a.err_cap = l.err_cap;
+            a.status = (uint32_t *)(ws + l.status_off) + 2 * pt;
+            a.stream = s;
+            a.pl = nullptr;
+            a.pipe_ws = nullptr;
+            a.tab = tabs[g];
+            a.k1_events = nullptr;
+            PipeArgs &pa = pas[i];
+            pa.nr = L.nr;
+            pa.seg = L.seg;
+            pa.gps = L.gps;
+            pa.nseg = L.nseg;
+            pa.nb = L.nb;
+            pa.cap = P.cap;
+            pa.band_lo = L.band_lo;
+            pa.lcap = P.lcap;
+            pa.rec_words = P.rec_words;
+            pa.tab = tabs[g];  // K2 and K3 read only the finder of a pick entry: the envelope's tables serve every point
+            pa.segsum = da.segsum;
+            pa.segcnt = da.segcnt;
+            pa.nslow = (const uint32_t *)(gw + G.nslow_off[i]);
+            pa.slots = (const uint32_t *)(gw + G.slots_off[i]);
+            pa.gsum = da.gsum;
+            pa.gend = da.gend;
+            pa.gcum = da.gcum;
+            pa.grec = da.grec;
+            pa.list = da.list;
+            pa.list_count = (const uint32_t *)(gw + G.counts_off) + i;
+            pa.recs = (uint32_t *)(gw + G.recs_off[i]);
+            sels[i] = (uint32_t *)(gw + G.sel_off[i]);
+        }
+        for (uint64_t off = 0; off < rpp; off += L.nr) {
+            const uint32_t cn = (rpp - off) < L.nr ? (uint32_t)(rpp - off) : L.nr;
+            // the envelope's list count and, right behind it, the points'
+            if (hipMemsetAsync(gw + L.count_off, 0, G.counts_off - L.count_off + 4 * (size_t)ng, s) != hipSuccess)
+                return MSIM_E_HIP;
+            da.run_begin = run_begin + off;
+            da.n = cn;
+            if (launch_draws(da, s) != hipSuccess) return MSIM_E_HIP;
+            for (uint32_t i0 = 0; i0 < ng; i0 += bound) {
+                SplitArgs sa;
+                memset(&sa, 0, sizeof(sa));
+                sa.nr = L.nr;
+                sa.nseg = L.nseg;
+                sa.cap = L.cap;
+                sa.lcap = L.lcap;
+                sa.np = ng - i0 < bound ? ng - i0 : bound;
+                sa.nslow = da.nslow;
+                sa.slots = da.slots;
+                sa.list = da.list;
+                sa.fthr = fthr + (size_t)(first + i0) * 16;
+                for (uint32_t i = 0; i < sa.np; ++i) {
+                    const PipeArgs &pa = pas[i0 + i];
+                    sa.pt[i] = SplitPoint{(uint32_t *)pa.nslow, (uint32_t *)pa.slots, sels[i0 + i],
+                                          (uint32_t *)pa.list_count, pa.cap, pa.lcap};
+                }
+                if (launch_sweep_split(sa, s) != hipSuccess) return MSIM_E_HIP;
+            }
+            for (uint32_t i = 0; i < ng; ++i)
+                if (launch_shared_tail(las[i], pas[i], sels[i], G.pl[i].k2_kind, (uint32_t)off, cn) != hipSuccess)
+                    return MSIM_E_HIP;
+        }
+        for (uint32_t i = 0; i < ng; ++i)
+            if (launch_shared_finish(las[i]) != hipSuccess) return MSIM_E_HIP;
+        first += ng;
+    }
+    return launch_sweep_status((const uint32_t *)(ws + l.status_off), np, (uint32_t *)d_status, s) == hipSuccess ? MSIM_OK
+                                                                                                                 : MSIM_E_HIP;
+}
+
 }  // namespace
 
 void msim::config_weights(const msim_config *cfg, std::vector<uint64_t> *w, uint32_t *total_weight)
@@ -1124,7 +1430,12 @@ int msim_run(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32
 
 int msim_sweep_create(const msim_config *const *cfgs, uint32_t n_points, msim_sweep **out)
 {
-    if (!cfgs || !out || n_points == 0) return MSIM_E_INVALID;
+    return msim_sweep_create_ex(cfgs, n_points, 0u, out);
+}
+
+int msim_sweep_create_ex(const msim_config *const *cfgs, uint32_t n_points, uint32_t flags, msim_sweep **out)
+{
+    if (!cfgs || !out || n_points == 0 || (flags & ~(uint32_t)MSIM_SWEEP_SHARED_DRAWS)) return MSIM_E_INVALID;
     msim_sweep *w = new (std::nothrow) msim_sweep();
     if (!w) return MSIM_E_INVALID;
     w->m = cfgs[0] ? cfgs[0]->n : 0;
@@ -1187,8 +1498,42 @@ int msim_sweep_create(const msim_config *const *cfgs, uint32_t n_points, msim_sw
         if (!getenv("MSIM_SWEEP_LISTED_ORDER"))  // A/B: the caller's point order
             for (auto &g : w->groups)
                 std::stable_sort(g.points.begin(), g.points.end(), [&](uint32_t a, uint32_t b) { return cost(a) > cost(b); });
+    } else if (flags & MSIM_SWEEP_SHARED_DRAWS) {
+        // the shared-draw form takes effect only when the honest pipeline takes every point; any other sweep keeps
+        // the per-lane kernel, and the flag changes nothing
+        bool all_pipe = !w->self;
+        for (uint32_t i = 0; i < n_points; ++i) all_pipe = all_pipe && cfgs[i]->pipe_ok;
+        if (all_pipe) {
+            const int rc = build_draw_groups(w, cfgs, n_points);
+            if (rc) {
+                delete w;
+                return rc;
+            }
+        }
     }
     *out = w;
+    return MSIM_OK;
+}
+
+int msim_sweep_group_of(const msim_sweep *sw, uint32_t point)
+{
+    return sw && sw->shared && point < sw->group_of.size() ? sw->group_of[point] : -1;
+}
+
+int msim_sweep_info(const msim_sweep *sw, uint64_t runs_per_point, msim_sweep_plan *out)
+{
+    if (!sw || !out || runs_per_point == 0 || runs_per_point * sw->pts.size() > msim::MAX_LAUNCH_RUNS) return MSIM_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->engine = sw->general ? 4u : sw->sel ? 3u : sw->shared ? 1u : 0u;
+    out->slice_runs = (uint32_t)runs_per_point;
+    if (sw->sel && !sw->general) out->slice_runs = sel_ws_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point, sw->max_duration).nr;
+    if (sw->shared) {
+        const SharedLayout l = shared_layout(sw, runs_per_point);
+        out->draw_groups = (uint32_t)sw->dgroups.size();
+        out->largest_group = l.largest;
+        out->slice_runs = l.slice_runs;
+    }
+    out->workspace_bytes = msim_sweep_workspace_bytes(sw, runs_per_point);
     return MSIM_OK;
 }
 
@@ -1205,6 +1550,7 @@ size_t msim_sweep_workspace_bytes(const msim_sweep *sw, uint64_t runs_per_point)
     if (!sw || runs_per_point == 0 || runs_per_point * sw->pts.size() > msim::MAX_LAUNCH_RUNS) return 0;
     if (sw->general) return gen_only_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point, sw->max_duration, sw->gen_full).total;
     if (sw->sel) return sel_ws_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point, sw->max_duration).total;
+    if (sw->shared) return shared_layout(sw, runs_per_point).total;
     return sweep_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point).total;
 }
 
@@ -1256,6 +1602,9 @@ int msim_sweep_launch(const msim_sweep *sw, uint64_t run_begin, uint64_t runs_pe
                                runs_per_point, seed_base, d_sums, d_per_run, d_best_height, d_status,
                                (hipStream_t)stream, nullptr);
     }
+    if (sw->shared)
+        return shared_launch_impl(sm, run_begin, runs_per_point, seed_base, d_sums, d_per_run, d_best_height, d_status,
+                                  (char *)d_workspace, workspace_bytes, (hipStream_t)stream);
     const SweepLayout l = sweep_layout(sw->m, np, runs_per_point);
     if (workspace_bytes < l.total) return MSIM_E_INVALID;
     const size_t pts_b = np * sizeof(msim::SimParams);

@@ -107,6 +107,33 @@ hipError_t launch_sweep(const SweepArgs &a)
     }
 }
 
+hipError_t launch_shared_tail(const LaunchArgs &a, const PipeArgs &pa, const uint32_t *sel, uint32_t k2_kind, uint32_t off,
+                              uint32_t cn)
+{
+    switch (a.p.m) {
+#define CASE(MM) \
+    case MM:     \
+        return launch_shared_tail_m##MM(a, pa, sel, k2_kind, off, cn);
+        MSIM_FOR_EACH_M(CASE)
+#undef CASE
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_shared_finish(const LaunchArgs &a)
+{
+    switch (a.p.m) {
+#define CASE(MM) \
+    case MM:     \
+        return launch_shared_finish_m##MM(a);
+        MSIM_FOR_EACH_M(CASE)
+#undef CASE
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_sel(const SelArgs &a, uint32_t m, uint32_t ns_class, hipStream_t s)
 {
     switch (m) {

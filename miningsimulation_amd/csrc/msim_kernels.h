@@ -6,6 +6,7 @@
 
 #include "msim_dispatch.h"
 #include "msim_pipeline.h"
+#include "msim_sweepsplit.h"
 
 namespace msim {
 
@@ -67,6 +68,21 @@ MSIM_FOR_EACH_M(MSIM_DECL_LAUNCH)
 hipError_t launch_finalize(const uint64_t *partials, uint32_t nparts, uint32_t nvals, uint64_t *out,
                            const uint32_t *retry_count, const uint32_t *fail_count, uint32_t retry_cap,
                            uint32_t *status, hipStream_t stream);
+// Shared-draw sweeps (msim_sweepsplit.h). One point of a draw group after K1 and S1 of a slice: K2 over the point's
+// index list (sel) and K3 over the slice's runs [off, off + cn), with the point's SimParams (a.p), record and
+// retry-list pointers (a) and its view of the workspace (pa); then, once per point after its last slice, the retry
+// kernel and the finalize, as a single network's launch.
+hipError_t launch_shared_tail(const LaunchArgs &a, const PipeArgs &pa, const uint32_t *sel, uint32_t k2_kind, uint32_t off,
+                              uint32_t cn);
+hipError_t launch_shared_finish(const LaunchArgs &a);
+#define MSIM_DECL_SHARED(MM)                                                                                         \
+    hipError_t launch_shared_tail_m##MM(const LaunchArgs &a, const PipeArgs &pa, const uint32_t *sel,            \
+                                        uint32_t k2_kind, uint32_t off, uint32_t cn);                              \
+    hipError_t launch_shared_finish_m##MM(const LaunchArgs &a);
+MSIM_FOR_EACH_M(MSIM_DECL_SHARED)
+#undef MSIM_DECL_SHARED
+hipError_t launch_sweep_split(const SplitArgs &a, hipStream_t s);  // S1 (msim_sweepsplit.hip)
+hipError_t launch_sweep_status(const uint32_t *st, uint32_t np, uint32_t *status, hipStream_t s);
 hipError_t launch_draws(const DrawArgs &a, hipStream_t s);
 hipError_t draws_blocks_per_cu(int *blocks);  // resident K1 workgroups per CU
 hipError_t launch_log1p(const double *x, double *out, uint64_t n, hipStream_t s);

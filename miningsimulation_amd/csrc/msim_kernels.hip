@@ -181,7 +181,8 @@ static_assert(K3_TPB % 64 == 0 && K3_TPB <= TPB && TPB % K3_TPB == 0, "K3 workgr
 constexpr int k2_waves(int m, int kind) { return kind == 0 ? (m <= 9 ? MSIM_K2_WAVES : m <= 14 ? 2 : 1) : (m <= 13 ? 2 : 1); }
 // The mid and full state machines at two waves per SIMD (256 VGPRs): at three (168) the mid one spilled 31
 // VGPRs, the full one 132; a rho > 0.002 network lists ~10x the lean one's blocks, so K2 still fills the chip.
-template <int M, int KIND>
+// SEL: a point of a shared-draw sweep (msim_sweepsplit.h): lane j runs the envelope's entry list[sel[j]].
+template <int M, int KIND, bool SEL = false>
 __global__ __launch_bounds__(K2_TPB) __attribute__((amdgpu_waves_per_eu(k2_waves(M, KIND), 8))) void msim_episode_kernel(const SimParams p,
                                                                                                     const PipeArgs a)
 {
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(K2_TPB) __attribute__((amdgpu_waves_per_eu(k2_waves
     la.tab.pick = &s_pick;
     const uint32_t cnt = *a.list_count;
     const uint32_t lim = cnt < a.lcap ? cnt : a.lcap;
-    for (uint32_t idx = blockIdx.x * K2_TPB + threadIdx.x; idx < lim; idx += gridDim.x * K2_TPB) episode_entry<M, KIND>(p, la, idx);
+    for (uint32_t idx = blockIdx.x * K2_TPB + threadIdx.x; idx < lim; idx += gridDim.x * K2_TPB) episode_entry<M, KIND, SEL>(p, la, idx);
 }
 
 // K3: one lane per run (msim_pipeline.h combine_run), then the MinerStats reduction.
@@ -384,6 +385,37 @@ static hipError_t launch_m(const LaunchArgs &a)
                            a.status, a.stream);
 }
 
+// A point of a shared-draw sweep (msim_kernels.h launch_shared_tail / launch_shared_finish).
+template <int M>
+static hipError_t launch_shared_tail_impl(const LaunchArgs &a, const PipeArgs &pa, const uint32_t *sel, uint32_t k2_kind,
+                                          uint32_t off, uint32_t cn)
+{
+    PipeArgs pk2 = pa;  // K2 reads the index list where K3 reads the slots (msim_pipeline.h episode_entry)
+    pk2.slots = sel;
+    PipeArgs pk3 = pa;  // MSIM_PIPE_FORCE_RETRY as in launch_pipeline
+    if (getenv("MSIM_PIPE_FORCE_RETRY") != nullptr) pk3.band_lo = pa.nseg;
+    uint32_t ep_grid = (pa.lcap + K2_TPB - 1) / K2_TPB;
+    if (ep_grid > 8192u * (TPB / K2_TPB)) ep_grid = 8192u * (TPB / K2_TPB);
+    if (ep_grid == 0) ep_grid = 1;
+    if (k2_kind == 0) hipLaunchKernelGGL((msim_episode_kernel<M, 0, true>), dim3(ep_grid), dim3(K2_TPB), 0, a.stream, a.p, pk2);
+    else hipLaunchKernelGGL((msim_episode_kernel<M, K2_KIND_HI, true>), dim3(ep_grid), dim3(K2_TPB), 0, a.stream, a.p, pk2);
+    hipLaunchKernelGGL((msim_combine_kernel<M>), dim3((cn + K3_TPB - 1) / K3_TPB), dim3(K3_TPB), 0, a.stream, a.p, pk3, cn,
+                       off, a.partials + (size_t)(off / K3_TPB) * 6 * M, a.records, a.best_h, a.err_count, a.err_list,
+                       a.err_cap);
+    return hipGetLastError();
+}
+
+template <int M>
+static hipError_t launch_shared_finish_impl(const LaunchArgs &a)
+{
+    const uint32_t nrow = (a.n + K3_TPB - 1) / K3_TPB, nbr = (a.err_cap + TPB - 1) / TPB;
+    launch_retry<M>(a, a.partials + (size_t)nrow * 6 * M, nbr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_finalize(a.partials, nrow + nbr, (uint32_t)(6 * M), a.sums, a.err_count, a.fail_count, a.err_cap, a.status,
+                           a.stream);
+}
+
 template <int M>
 static hipError_t launch_sweep_impl(const SweepArgs &a)
 {
@@ -414,6 +446,12 @@ static hipError_t launch_sweep_impl(const SweepArgs &a)
 #define MSIM_CAT(a, b) MSIM_CAT2(a, b)
 hipError_t MSIM_CAT(launch_runs_m, MSIM_M)(const LaunchArgs &a) { return launch_m<MSIM_M>(a); }
 hipError_t MSIM_CAT(launch_sweep_m, MSIM_M)(const SweepArgs &a) { return launch_sweep_impl<MSIM_M>(a); }
+hipError_t MSIM_CAT(launch_shared_tail_m, MSIM_M)(const LaunchArgs &a, const PipeArgs &pa, const uint32_t *sel,
+                                                  uint32_t k2_kind, uint32_t off, uint32_t cn)
+{
+    return launch_shared_tail_impl<MSIM_M>(a, pa, sel, k2_kind, off, cn);
+}
+hipError_t MSIM_CAT(launch_shared_finish_m, MSIM_M)(const LaunchArgs &a) { return launch_shared_finish_impl<MSIM_M>(a); }
 #endif
 
 }  // namespace msim

@@ -877,10 +877,13 @@ MSIM_HD bool combine_run(const SimParams &p, const PipeArgs &a, uint32_t r, uint
 }
 
 // ---------------------------------------------------------------- K2 lane body (shared host/device)
-template <int M, int KIND>
+// SEL (shared-draw sweeps, msim_sweepsplit.h): K2 is handed the point's index list sel_p in a.slots (K2 reads no
+// slots otherwise, and PipeArgs stays what the plain pipeline passes): entry idx of it names the listed block of the
+// envelope's list; the record, list_count and lcap are the point's own.
+template <int M, int KIND, bool SEL = false>
 MSIM_HD void episode_entry(const SimParams &p, const PipeArgs &a, uint32_t idx)
 {
-    const EpEntry e = a.list[idx];
+    const EpEntry e = a.list[SEL ? a.slots[idx] : idx];
     if (e.run == EP_HOLE) return;  // never referenced by a run's slots
     uint32_t *rec = a.recs + (size_t)idx * a.rec_words;
     rec[2 + 2 * M] = e.block;

@@ -20,7 +20,8 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import MsimCross, MsimMiner, MsimMoments, MsimRunRecord, MsimStats, MsimSums, MsimTiming, check, lib
+from ._lib import (MSIM_SWEEP_SHARED_DRAWS, MsimCross, MsimMiner, MsimMoments, MsimRunRecord, MsimStats, MsimSums,
+                   MsimSweepPlan, MsimTiming, check, lib)
 from .contrasts import CROSS_WORDS, Pair, cross_from_words, pairs_struct
 from .moments import MOMENT_WORDS, HistSpec, moments_from_words
 
@@ -346,15 +347,33 @@ class Sweep:
 
     The reference covers a grid by editing SetupMiners (main.cpp:44-65) and rebuilding per point
     (README.md:21-27). Point p, run r of a sweep is bit-identical to Simulation(points[p]).run for run
-    run_begin + r: every point sees the same seeds."""
+    run_begin + r: every point sees the same seeds.
 
-    def __init__(self, points: Sequence[Sequence[Miner]], duration_ms: int = SIM_DURATION_MS):
+    shared_draws=True asks for the shared-draw form (msim_sweep_create_ex, MSIM_SWEEP_SHARED_DRAWS): honest points
+    with the same weights share ONE draw pass per slice; only the short per-point tails run per point. Same
+    results, bit for bit; a sweep the form does not serve (a selfish point, a delay the pipeline does not take)
+    runs as without it. plan() tells which engine serves the sweep."""
+
+    def __init__(self, points: Sequence[Sequence[Miner]], duration_ms: int = SIM_DURATION_MS,
+                 shared_draws: bool = False):
         self.sims = [Simulation(p, duration_ms) for p in points]
         self.m = len(self.sims[0].miners)
         handles = (ctypes.c_void_p * len(self.sims))(*[s.handle.value for s in self.sims])
         h = ctypes.c_void_p()
-        check(lib.msim_sweep_create(handles, len(self.sims), ctypes.byref(h)), "msim_sweep_create")
+        check(lib.msim_sweep_create_ex(handles, len(self.sims), MSIM_SWEEP_SHARED_DRAWS if shared_draws else 0,
+                                       ctypes.byref(h)), "msim_sweep_create_ex")
         self._h = h
+
+    def plan(self, runs_per_point: int) -> dict:
+        """msim_sweep_info: engine (0 per-lane kernel, 1 shared-draw pipeline, 3 entity engine, 4 general engine),
+        draw_groups, largest_group, slice_runs, workspace_bytes. Host only."""
+        pl = MsimSweepPlan()
+        check(lib.msim_sweep_info(self._h, runs_per_point, ctypes.byref(pl)), "msim_sweep_info")
+        return {f: int(getattr(pl, f)) for f, _ in MsimSweepPlan._fields_}
+
+    def group_of(self, p: int) -> int:
+        """The draw group of point p, or -1 when the sweep does not run in the shared-draw form. Host only."""
+        return int(lib.msim_sweep_group_of(self._h, p))
 
     def __len__(self) -> int:
         return len(self.sims)
@@ -443,6 +462,15 @@ class Sweep:
         check(lib.msim_sweep_launch(self._h, run_begin, runs_per_point, seed_base & 0xFFFFFFFF, ptr(d_sums),
                                     ptr(d_per_run), ptr(d_best_height), ptr(d_status), ptr(d_workspace),
                                     d_workspace.numel(), sh), "msim_sweep_launch")
+
+
+def propagation_sweep(miners: Sequence[Miner], delays_ms: Sequence[int], duration_ms: int = SIM_DURATION_MS) -> Sweep:
+    """One network at several uniform propagation delays (the reference's first example, README.md:21-27: the
+    same hashrates at 10 s and at 100 ms, one rebuild each) as a shared-draw sweep: point i is `miners` with every
+    propagation_ms = delays_ms[i]. All points share their draws, so run_contrasts(..., pairs_vs_baseline(...))
+    gives the differences between delays with the per-run difference's error."""
+    points = [[Miner(mn.id, mn.perc, int(d), mn.is_selfish) for mn in miners] for d in delays_ms]
+    return Sweep(points, duration_ms, shared_draws=True)
 
 
 def timing_enable(on: bool = True) -> None:
