@@ -109,7 +109,19 @@ int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t du
  * A fourth, MSIM_MOMENTS_CHUNK_RUNS=<n> (n > 0), read only by msim_run_moments, msim_sweep_run_moments,
  * msim_run_contrasts and msim_sweep_run_contrasts at every call: a chunk of runs whose records stay in device
  * memory holds at most n runs (per point), so a few hundred runs exercise the chunk loop and its limb-by-limb
- * addition. */
+ * addition.
+ * Five more, MSIM_PIPE_TEST_*, read at every sizing and launch call of the honest pipeline (single networks and
+ * shared-draw sweeps). Each only ever lowers a capacity below its 8-sigma size (the smaller of the natural value and
+ * n, n > 0), and does so in the layout computation, so the buffers are exactly as large as the kernels are told:
+ *   MSIM_PIPE_TEST_CAP=<n>         slow-block slots per (run, segment) of the pipeline's layout and of a shared-draw
+ *                                  group's envelope layout
+ *   MSIM_PIPE_TEST_LCAP=<n>        episode-list length of the same two
+ *   MSIM_PIPE_TEST_POINT_CAP=<n>   the slots per (run, segment) of every point of a shared-draw group
+ *   MSIM_PIPE_TEST_POINT_LCAP=<n>  the index-list length of every point of a shared-draw group
+ *   MSIM_PIPE_TEST_K2_KIND=<0|1>   the episode kernel's state machine (0 lean, 1 mid) for every one of those layouts,
+ *                                  whatever the network's rho; any other value is ignored
+ * A run that outgrows a lowered capacity is flagged and recomputed by the retry kernel like any other, so results
+ * stay the same and status[0] counts the retried runs. Unset, nothing changes. */
 int msim_config_is_wide(const msim_config *cfg);
 /* How many launches of this config the caller keeps in flight at once (default 1; e.g. 2 when steps
  * alternate over two HIP streams). The event-skipping pipeline plans its draw kernel's grid for it: three

@@ -213,6 +213,27 @@ uint32_t max_slice_runs()
     return v >= (1ll << 22) ? 1u << 22 : (uint32_t)align256((size_t)v);
 }
 
+// Test switches (MSIM_PIPE_TEST_CAP, MSIM_PIPE_TEST_LCAP, MSIM_PIPE_TEST_POINT_CAP, MSIM_PIPE_TEST_POINT_LCAP,
+// MSIM_PIPE_TEST_K2_KIND; msim.h): capacities of the honest pipeline lowered so that a few hundred runs overflow them
+// and take the retry path, as MSIM_MAX_SLICE_RUNS makes the slice loops reachable. Read at every sizing and launch
+// call. point: the per-point layouts of a shared-draw group (cap_p, lcap_p); otherwise the plain pipeline's layout and
+// a group's envelope layout. The limits go into the layout computation (msim_pipeline.h PipeLimits), so offsets,
+// workspace sizes and every kernel's arguments come from the same lowered values.
+msim::PipeLimits pipe_test_limits(bool point)
+{
+    auto num = [](const char *name) {
+        const char *e = getenv(name);
+        const long long v = e ? atoll(e) : 0;
+        return v <= 0 ? 0u : v >= 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)v;
+    };
+    msim::PipeLimits lim;
+    lim.cap = num(point ? "MSIM_PIPE_TEST_POINT_CAP" : "MSIM_PIPE_TEST_CAP");
+    lim.lcap = num(point ? "MSIM_PIPE_TEST_POINT_LCAP" : "MSIM_PIPE_TEST_LCAP");
+    if (const char *e = getenv("MSIM_PIPE_TEST_K2_KIND"))
+        if ((e[0] == '0' || e[0] == '1') && e[1] == '\0') lim.k2_kind = e[0] - '0';
+    return lim;
+}
+
 // K1 wave slots of the current device (CUs x resident K1 waves per CU); 8192 if it cannot be queried.
 uint32_t draw_slots()
 {
@@ -234,9 +255,10 @@ msim::PipeLayout pipe_layout(const msim_config *c, uint64_t n_runs)
     const uint32_t jobs = c->jobs ? c->jobs : 1u;
     uint32_t slots = jobs == 1u ? draw_slots() * 3u : draw_slots() * 2u / jobs;
     if (slots < 1u) slots = 1u;
-    const msim::PipeLayout L = msim::pipe_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, PIPE_SLICE_BUDGET, slots);
+    const msim::PipeLimits lim = pipe_test_limits(false);
+    const msim::PipeLayout L = msim::pipe_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, PIPE_SLICE_BUDGET, slots, 0.0, lim);
     const uint32_t cap = max_slice_runs();  // the layout of a slice of exactly `cap` runs, not a smaller budget's
-    return cap && L.nr > cap ? msim::pipe_layout_nr(c->rho, c->n, c->p.duration_ms, cap, slots) : L;
+    return cap && L.nr > cap ? msim::pipe_layout_nr(c->rho, c->n, c->p.duration_ms, cap, slots, lim) : L;
 }
 
 // Pipeline tables for this config on the current device: pick table, log table, jump matrices for
@@ -947,12 +969,13 @@ SharedGroupLayout shared_group_nr(const msim_sweep *sw, const msim_sweep::DrawGr
 {
     SharedGroupLayout L;
     const int64_t D = dg.env->p.duration_ms;
-    L.env = msim::pipe_layout_nr(dg.env->rho, sw->m, D, nr, slots);
+    L.env = msim::pipe_layout_nr(dg.env->rho, sw->m, D, nr, slots, pipe_test_limits(false));
     size_t o = L.env.total;
     L.counts_off = o;
     o = align256(o + 4 * dg.points.size());
+    const msim::PipeLimits plim = pipe_test_limits(true);  // cap_p, lcap_p, K2's kind: sized below from the lowered values
     for (uint32_t pt : dg.points) {
-        const msim::PipeLayout P = msim::pipe_layout_nr(sw->rhos[pt], sw->m, D, nr, slots);
+        const msim::PipeLayout P = msim::pipe_layout_nr(sw->rhos[pt], sw->m, D, nr, slots, plim);
         L.pl.push_back(P);
         L.nslow_off.push_back(o);
         o = align256(o + (size_t)P.nseg * nr * 4);

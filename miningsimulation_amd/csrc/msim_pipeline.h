@@ -143,19 +143,28 @@ enum : uint32_t { REC_ENDED = 1u, REC_ERR = 2u, REC_SKIP = 4u };
 // `slots` = wave slots of K1 on the device (CUs x resident waves per CU). The run is cut into `nseg`
 // workers of `seg` blocks so that the K1 grid fills the device in whole rounds: every wave does the
 // same work, so a partial last round would leave SIMDs idle.
-// The layout of a slice of exactly nr runs (a multiple of 256): K2's episode records, band records per group.
-inline PipeLayout pipe_layout_nr(double rho, uint32_t m, int64_t duration_ms, uint32_t nr, uint32_t slots)
+
+// Test limits (msim.h MSIM_PIPE_TEST_*): capacities a test lowers below their 8-sigma sizes so that a few hundred
+// runs reach the overflow branches of K1, S1, K2 and K3. A limit only ever lowers (min with the natural value), and it
+// enters here, before the offsets are laid out, so the buffers and every kernel argument agree on it.
+struct PipeLimits {
+    uint32_t cap = 0, lcap = 0;  // 0: the natural capacity
+    int32_t k2_kind = -1;        // 0 lean or 1 mid: K2's state machine whatever rho says; anything else: by rho
+};
+
+// Blocks to pre-generate per run (P(more) < 1e-15 per run).
+inline double pipe_need(int64_t duration_ms)
 {
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    PipeLayout L;
-    const double D = (double)duration_ms;
-    const double mu = D / 599999.5, sd = sqrt(mu > 1.0 ? mu : 1.0);
-    const double need = mu + 8.0 * sd + 64.0;  // blocks to pre-generate (P(more) < 1e-15 per run)
-    L.rec_words = 3 + 2 * m;
-    L.k2_kind = rho <= K2_LEAN_RHO ? 0u : K2_KIND_HI;
-    L.nr = nr;
-    // workers per run: minimise rounds(w) * (seg(w) + jump cost), jump ~ 25 blocks of work
-    const double rows = L.nr / 64.0;
+    const double mu = (double)duration_ms / 599999.5, sd = sqrt(mu > 1.0 ? mu : 1.0);
+    return mu + 8.0 * sd + 64.0;
+}
+
+// Workers per run for a slice of nr runs on `slots` wave slots: minimise rounds(w) * (seg(w) + jump cost), jump ~ 25
+// blocks of work.
+inline uint32_t pipe_workers(int64_t duration_ms, uint32_t nr, uint32_t slots)
+{
+    const double need = pipe_need(duration_ms);
+    const double rows = nr / 64.0;
     if (slots < 1) slots = 1;
     uint32_t best_w = 1;
     double best_f = 1e300;
@@ -169,8 +178,25 @@ inline PipeLayout pipe_layout_nr(double rho, uint32_t m, int64_t duration_ms, ui
             best_w = w;
         }
     }
-    L.nseg = best_w;
-    L.seg = (uint32_t)ceil(need / best_w / GROUP) * GROUP;
+    return best_w;
+}
+
+// The layout of a slice of exactly nr runs (a multiple of 256) cut into nseg workers per run: K2's episode records,
+// band records per group.
+inline PipeLayout pipe_layout_w(double rho, uint32_t m, int64_t duration_ms, uint32_t nr, uint32_t nseg,
+                                const PipeLimits &lim = PipeLimits())
+{
+    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    PipeLayout L;
+    const double D = (double)duration_ms;
+    const double mu = D / 599999.5, sd = sqrt(mu > 1.0 ? mu : 1.0);
+    const double need = pipe_need(duration_ms);
+    L.rec_words = 3 + 2 * m;
+    L.k2_kind = rho <= K2_LEAN_RHO ? 0u : K2_KIND_HI;
+    if (lim.k2_kind == 0 || lim.k2_kind == 1) L.k2_kind = (uint32_t)lim.k2_kind;
+    L.nr = nr;
+    L.nseg = nseg;
+    L.seg = (uint32_t)ceil(need / nseg / GROUP) * GROUP;
     if (L.seg < GROUP) L.seg = GROUP;
     L.gps = L.seg / GROUP;
     L.nsg = (L.gps + SGROUP - 1) / SGROUP;
@@ -181,6 +207,7 @@ inline PipeLayout pipe_layout_nr(double rho, uint32_t m, int64_t duration_ms, ui
     L.nband = L.nseg - L.band_lo;
     const double lam = rho * L.seg;
     L.cap = (uint32_t)ceil(lam + 8.0 * sqrt(lam) + 8.0);
+    if (lim.cap && lim.cap < L.cap) L.cap = lim.cap;
     const double ent = (double)L.nr * rho * L.nb;
     // A K1 wave reserves list slots a chunk at a time: one same-address atomic per chunk instead of one per
     // append (at rho = 1.7 % — configs[0] — the per-append atomics serialised K1 to 30x its draw time). The
@@ -190,6 +217,7 @@ inline PipeLayout pipe_layout_nr(double rho, uint32_t m, int64_t duration_ms, ui
     while (L.lchunk < 256 && L.lchunk < per_wave / 4.0) L.lchunk *= 2;
     const double holes = (double)(L.nr / 64) * L.nseg * L.lchunk;
     L.lcap = (uint32_t)ceil(ent + 8.0 * sqrt(ent) + 1024.0 + holes);
+    if (lim.lcap && lim.lcap < L.lcap) L.lcap = lim.lcap;
     size_t o = 0;
     L.segsum_off = o;
     o = al(o + (size_t)L.nseg * L.nr * 8);
@@ -218,13 +246,20 @@ inline PipeLayout pipe_layout_nr(double rho, uint32_t m, int64_t duration_ms, ui
     return L;
 }
 
+// The same with the workers per run chosen for `slots` wave slots (pipe_workers).
+inline PipeLayout pipe_layout_nr(double rho, uint32_t m, int64_t duration_ms, uint32_t nr, uint32_t slots,
+                                 const PipeLimits &lim = PipeLimits())
+{
+    return pipe_layout_w(rho, m, duration_ms, nr, pipe_workers(duration_ms, nr, slots), lim);
+}
+
 // The largest slice (all n_runs, or fewer) whose layout, plus extra_per_run bytes per run, fits the budget.
 inline PipeLayout pipe_layout_for(double rho, uint32_t m, int64_t duration_ms, uint64_t n_runs, double budget,
-                                  uint32_t slots, double extra_per_run = 0.0)
+                                  uint32_t slots, double extra_per_run = 0.0, const PipeLimits &lim = PipeLimits())
 {
     uint64_t nr = (n_runs + 255) / 256 * 256;
     for (;;) {
-        const PipeLayout L = pipe_layout_nr(rho, m, duration_ms, (uint32_t)nr, slots);
+        const PipeLayout L = pipe_layout_nr(rho, m, duration_ms, (uint32_t)nr, slots, lim);
         const double tot = (double)L.total + extra_per_run * (double)nr;
         if (tot <= budget || nr <= 256) return L;
         uint64_t next = (uint64_t)((double)nr * budget / tot * 0.98) / 256 * 256;

@@ -142,7 +142,7 @@ template <int M>
 int shared_run(const uint64_t *perc, const int64_t *props, uint32_t np, int64_t duration_ms, uint32_t seed_base,
                uint64_t run_begin, uint32_t n, uint32_t wave_slots, uint32_t env_cap, uint32_t env_lcap,
                const uint32_t *pt_cap, const uint32_t *pt_lcap, uint32_t max_group, uint32_t *found, uint32_t *stale,
-               uint8_t *ok, uint8_t *listing_ok, uint32_t *n_env_entries)
+               uint8_t *ok, uint8_t *listing_ok, uint32_t *n_env_entries, int k2_kind = -1)
 {
     if (max_group == 0 || max_group > SPLIT_MAX_POINTS) max_group = SPLIT_MAX_POINTS;
     std::vector<uint8_t> self((size_t)M, 0);
@@ -156,6 +156,10 @@ int shared_run(const uint64_t *perc, const int64_t *props, uint32_t np, int64_t 
     const PipeLayout &L = E.L;
     const uint32_t elcap = env_lcap ? env_lcap : 0xFFFFFFF0u;
     *n_env_entries = (uint32_t)E.list.size();
+    if (E.list.size() > elcap) {  // exactly elcap entries, as the device's buffer: an unguarded index fails under ASan
+        std::vector<EpEntry> cut(E.list.begin(), E.list.begin() + elcap);
+        E.list.swap(cut);
+    }
     if (E.list.empty()) E.list.push_back(EpEntry{});  // a valid pointer for record 0's masked reads
 
     // per point state
@@ -172,7 +176,7 @@ int shared_run(const uint64_t *perc, const int64_t *props, uint32_t np, int64_t 
         const PipeLayout Lp = pipe_layout_nr(rho_of(perc, pp, M), M, duration_ms, (n + 255) / 256 * 256, wave_slots);
         P[p].cap = pt_cap && pt_cap[p] ? pt_cap[p] : Lp.cap;
         P[p].lcap = pt_lcap && pt_lcap[p] ? pt_lcap[p] : (uint32_t)E.list.size() + 1u;
-        P[p].k2_kind = Lp.k2_kind;
+        P[p].k2_kind = k2_kind >= 0 && k2_kind <= 2 ? (uint32_t)k2_kind : Lp.k2_kind;
         P[p].count = 0;
         P[p].nslow.assign((size_t)L.nseg * n, 0xDEADBEEFu);
         P[p].slots.assign((size_t)L.nseg * P[p].cap * n, 0xFFFFFFFFu);
@@ -291,12 +295,13 @@ int shared_run(const uint64_t *perc, const int64_t *props, uint32_t np, int64_t 
 inline int shared_run_m(int m, const uint64_t *perc, const int64_t *props, uint32_t np, int64_t duration_ms,
                         uint32_t seed_base, uint64_t run_begin, uint32_t n, uint32_t wave_slots, uint32_t env_cap,
                         uint32_t env_lcap, const uint32_t *pt_cap, const uint32_t *pt_lcap, uint32_t max_group,
-                        uint32_t *found, uint32_t *stale, uint8_t *ok, uint8_t *listing_ok, uint32_t *n_env_entries)
+                        uint32_t *found, uint32_t *stale, uint8_t *ok, uint8_t *listing_ok, uint32_t *n_env_entries,
+                        int k2_kind = -1)
 {
 #define CASE(MM) \
     case MM:     \
         return shared_run<MM>(perc, props, np, duration_ms, seed_base, run_begin, n, wave_slots, env_cap, env_lcap, pt_cap, \
-                              pt_lcap, max_group, found, stale, ok, listing_ok, n_env_entries);
+                              pt_lcap, max_group, found, stale, ok, listing_ok, n_env_entries, k2_kind);
     switch (m) {
         MSIM_FOR_EACH_M(CASE)
     default:
