@@ -121,7 +121,13 @@ int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t du
  *   MSIM_PIPE_TEST_K2_KIND=<0|1>   the episode kernel's state machine (0 lean, 1 mid) for every one of those layouts,
  *                                  whatever the network's rho; any other value is ignored
  * A run that outgrows a lowered capacity is flagged and recomputed by the retry kernel like any other, so results
- * stay the same and status[0] counts the retried runs. Unset, nothing changes. */
+ * stay the same and status[0] counts the retried runs. Unset, nothing changes.
+ * Two more, for the large-network pipeline (single networks and sweeps), read at every sizing and launch call; they
+ * too only ever lower (the smaller of the natural value and n, n > 0) and act in the layout computation:
+ *   MSIM_WIDE_TEST_RCAP=<n>        candidate slots per run of a plain wide launch and of a shared-draw group's envelope
+ *   MSIM_WIDE_TEST_POINT_RCAP=<n>  candidate slots per run of every point of a shared-draw group of more than one point
+ * The large-network pipeline has no retry kernel: a run that outgrows a capacity fails (status[1] counts it, its
+ * records stay unwritten, msim_run / msim_sweep_run return MSIM_E_CAPACITY). Unset, nothing changes. */
 int msim_config_is_wide(const msim_config *cfg);
 /* How many launches of this config the caller keeps in flight at once (default 1; e.g. 2 when steps
  * alternate over two HIP streams). The event-skipping pipeline plans its draw kernel's grid for it: three
@@ -201,7 +207,12 @@ int msim_device_picks(const msim_config *cfg, const uint64_t *d_uniform, int32_t
  * every point of a grid in ONE device launch, one lane per (point, run). Point p, run r gives exactly
  * the result of msim_run(cfgs[p], run_begin, ...) for run run_begin + r (same seeds for every point).
  * All points must have the same miner count. Sums / records are point-major:
- *   sums[p * M + k], per_run[(p * runs_per_point + r) * M + k], best_height[p * runs_per_point + r]. */
+ *   sums[p * M + k], per_run[(p * runs_per_point + r) * M + k], best_height[p * runs_per_point + r].
+ * The points are either all narrow (at most MSIM_MAX_MINERS miners with percentages) or all on the large-network
+ * pipeline (msim_config_is_wide: more than MSIM_MAX_MINERS honest miners, or integer weights with W != 100; engine 2
+ * below); a sweep mixing the two is MSIM_E_INVALID, unless some point runs on the general engine, which then serves
+ * every point. A sweep of large-network points is one plain launch of that pipeline per point (into the sweep's
+ * outputs, one workspace), or the shared-draw form below. */
 typedef struct msim_sweep msim_sweep;
 int msim_sweep_create(const msim_config *const *cfgs, uint32_t n_points, msim_sweep **out);
 /* msim_sweep_create with flags (0: exactly msim_sweep_create; unknown bits: MSIM_E_INVALID).
@@ -217,7 +228,16 @@ int msim_sweep_create(const msim_config *const *cfgs, uint32_t n_points, msim_sw
  * split (its point with the largest delay leaves it) until it does.
  * A test switch, MSIM_SWEEP_SHARED_MAX_GROUP=<n> (0 < n < 8), read at every launch: a split pass serves at most n
  * points of a group, so a group of five takes the further split passes (never further draw passes) that otherwise
- * begin past 8 points. */
+ * begin past 8 points.
+ * Sweeps of large-network points (engine 2) take the flag too: points with equal weights, equal W and equal duration
+ * form a draw group; per group and slice the draw kernel W1 runs once on the envelope network, a split kernel derives
+ * each point's candidate list from the envelope's, and the episode and combine kernels run per point. A group whose
+ * envelope the large-network pipeline does not take (its fork rate is past what the combine kernel's LDS holds) loses
+ * its point with the largest delay to a group of its own until it is taken; a group of one is the plain launch.
+ * Results are those of the flags-0 sweep bit for bit, with ONE exception: that pipeline has no retry kernel, and a run
+ * whose ENVELOPE candidate list overflows its (8-sigma) capacity fails at every point of the group, so the shared form
+ * can fail a run (status[1], MSIM_E_CAPACITY) that the point's own launch would not. A point's own list overflows
+ * exactly when its own launch's would, and fails the run at that point only. */
 #define MSIM_SWEEP_SHARED_DRAWS 1u
 int msim_sweep_create_ex(const msim_config *const *cfgs, uint32_t n_points, uint32_t flags, msim_sweep **out);
 /* Host only, no device: the draw group of a point (0 .. draw_groups - 1), or -1 when the sweep does not run in the
@@ -227,11 +247,12 @@ int msim_sweep_group_of(const msim_sweep *sweep, uint32_t point);
 /* How msim_sweep_launch will execute runs_per_point runs of every point, as msim_pipeline_info for a config (the
  * reference: one rebuild per point, README.md:21-27). */
 typedef struct msim_sweep_plan {
-    uint32_t engine;          /* 0: per-lane kernel, one lane per (point, run); 1: shared-draw pipeline; 3: entity
+    uint32_t engine;          /* 0: per-lane kernel, one lane per (point, run); 1: shared-draw pipeline; 2: large-network
+                                 pipeline (msim_pipeline_info's value for it), with or without shared draws; 3: entity
                                  engine (a point with selfish miners); 4: general engine */
-    uint32_t draw_groups;     /* engine 1: draw passes per slice; else 0 */
-    uint32_t largest_group;   /* engine 1: points of the largest draw group; else 0 */
-    uint32_t slice_runs;      /* runs per point and slice (engine 1: of the group with the smallest slices) */
+    uint32_t draw_groups;     /* engines 1, 2: draw passes per slice (engine 2 with flags 0: n_points); else 0 */
+    uint32_t largest_group;   /* engines 1, 2: points of the largest draw group (engine 2 with flags 0: 1); else 0 */
+    uint32_t slice_runs;      /* runs per point and slice (engines 1, 2: of the group with the smallest slices) */
     uint64_t workspace_bytes; /* msim_sweep_workspace_bytes */
 } msim_sweep_plan;
 int msim_sweep_info(const msim_sweep *sweep, uint64_t runs_per_point, msim_sweep_plan *out);

@@ -23,6 +23,7 @@
 #include "msim_sel_launch.h"
 #include "msim_timing.h"
 #include "msim_wide_launch.h"
+#include "msim_widesplit.h"
 
 using msim::align256;
 
@@ -49,6 +50,7 @@ enum TableKey : uint64_t {
     TAB_GEN = 3ull << 32,       // GenParams of every point + arrays
     TAB_POINTS = 4ull << 32,    // SimParams[n_points]
     TAB_SPLIT = 5ull << 32,     // shared-draw sweeps: the points' split thresholds, [16] each, in draw-group order
+    TAB_WSPLIT = 6ull << 32,    // wide shared-draw sweeps: the points' delays [np][m] i64, then thresholds [np][m] u32
 };
 
 // A network as the general engine reads it (msim_general.h): integer weights summing to W.
@@ -147,9 +149,15 @@ struct msim_sweep {
     std::vector<DrawGroup> dgroups;
     std::vector<int32_t> group_of;  // per point
     std::vector<double> rhos;       // per point (its capacities and its K2 kind follow its own rho)
+    // Sweeps of large-network points (every point wide && !general; msim_widesplit.h): the sweep's own wide config
+    // of every point (the plain wide launch of a group of one), and the draw groups in dgroups (env: the envelope's
+    // wide config; null for a group of one). flags 0: every point a group of its own, `shared` stays false.
+    bool wide = false;
+    std::vector<msim_config *> wcfg;
     ~msim_sweep()
     {
         for (auto &g : dgroups) delete g.env;
+        for (auto *c : wcfg) delete c;
     }
 };
 
@@ -311,9 +319,20 @@ int global_log_table(const msim::LogTab **out, const msim::K1Log **k1 = nullptr)
 
 constexpr double WIDE_SLICE_BUDGET = 16.0 * (1ull << 30);
 
+// Test switches (msim.h): MSIM_WIDE_TEST_RCAP=<n> lowers the candidate capacity of a plain wide launch and of a
+// shared-draw group's envelope, MSIM_WIDE_TEST_POINT_RCAP=<n> every point's of such a group. They only ever lower
+// (wide_rcap) and act in the layout computation, so buffers and kernel arguments agree. 0: unset.
+uint32_t wide_test_rcap(bool point)
+{
+    const char *e = getenv(point ? "MSIM_WIDE_TEST_POINT_RCAP" : "MSIM_WIDE_TEST_RCAP");
+    const long long v = e ? atoll(e) : 0;
+    return v <= 0 ? 0u : v >= 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)v;
+}
+
 msim::WideLayout wide_layout(const msim_config *c, uint64_t n_runs)
 {
-    return msim::wide_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, WIDE_SLICE_BUDGET, max_slice_runs());
+    return msim::wide_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, WIDE_SLICE_BUDGET, max_slice_runs(),
+                                 wide_test_rcap(false));
 }
 
 // Device tables of a wide config (msim_wide_launch.h WideArgs) on the current device, uploaded once.
@@ -720,8 +739,10 @@ int sel_config_tables(msim_config *c, const msim::SelParams **pts, const uint32_
 }
 
 // Validate a miner list with integer weights summing to total_weight and build the config.
+// want_wide: the large-network pipeline for an honest network whatever MSIM_FORCE_WIDE says at this moment (the
+// internal configs of a wide sweep: its points may be W = 100 networks that were forced wide when they were created).
 int config_create_impl(const msim_miner *miners, uint32_t n, int64_t duration_ms, uint64_t total_weight,
-                       msim_config **out)
+                       msim_config **out, bool want_wide = false)
 {
     if (!miners || !out || n == 0 || duration_ms < 0 || total_weight == 0) return MSIM_E_INVALID;
     if (total_weight >= (1ull << 31)) return MSIM_E_WEIGHTS;
@@ -764,7 +785,7 @@ int config_create_impl(const msim_miner *miners, uint32_t n, int64_t duration_ms
     if (gen && !msim::gen_fits(n, duration_ms, gen_full)) return MSIM_E_MINERS;
     const bool sel = nself > 0 && !gen;
     const bool narrow = n <= MSIM_MAX_MINERS && (total_weight == 100 || sel);
-    const bool force_wide = getenv("MSIM_FORCE_WIDE") != nullptr && nself == 0;
+    const bool force_wide = (want_wide || getenv("MSIM_FORCE_WIDE") != nullptr) && nself == 0;
     msim_config *c = new (std::nothrow) msim_config();
     if (!c) return MSIM_E_INVALID;
     c->n = n;
@@ -1174,6 +1195,190 @@ int shared_launch_impl(msim_sweep *sw, uint64_t run_begin, uint64_t rpp, uint32_
                                                                                                                  : MSIM_E_HIP;
 }
 
+// ---------------------------------------------------------------- sweeps on the large-network pipeline (msim_widesplit.h)
+// The sweep's own wide config of every point, and its draw groups. shared: points with equal weights, equal W and
+// equal duration form a group; a group whose envelope the wide pipeline does not take (its W3 LDS is past 160 KiB:
+// config_create_impl marks it general) loses its point with the largest delay to a group of its own until it is
+// taken. Without `shared` every point is a group of its own. A group of one is the plain wide launch (env: null).
+int build_wide_groups(msim_sweep *w, const msim_config *const *cfgs, uint32_t np, bool shared)
+{
+    auto wide_copy = [](const msim_config *c, const std::vector<int64_t> &prop, msim_config **out) {
+        std::vector<msim_miner> ms(c->n);
+        for (uint32_t k = 0; k < c->n; ++k) ms[k] = msim_miner{c->wids[k], c->wperc[k], prop[k], 0};
+        const int rc = config_create_impl(ms.data(), c->n, c->p.duration_ms, c->total_weight, out, true);
+        if (rc == MSIM_OK && !(*out)->wide) {  // MSIM_FORCE_GENERAL at this moment
+            delete *out;
+            *out = nullptr;
+            return (int)MSIM_E_INVALID;
+        }
+        return rc;
+    };
+    w->wide = true;
+    w->group_of.assign(np, -1);
+    for (uint32_t i = 0; i < np; ++i) {
+        msim_config *c = nullptr;
+        const int rc = wide_copy(cfgs[i], cfgs[i]->wprop, &c);
+        if (rc) return rc;
+        w->wcfg.push_back(c);
+        if (c->general) return MSIM_E_INVALID;
+        w->rhos.push_back(c->rho);
+    }
+    if (!shared) {
+        for (uint32_t i = 0; i < np; ++i) w->dgroups.push_back({{i}, nullptr});
+        return MSIM_OK;
+    }
+    std::vector<std::vector<uint32_t>> work;
+    for (uint32_t i = 0; i < np; ++i) {
+        bool placed = false;
+        for (auto &g : work) {
+            const msim_config *f = cfgs[g[0]];
+            if (f->p.duration_ms == cfgs[i]->p.duration_ms && f->total_weight == cfgs[i]->total_weight &&
+                f->wperc == cfgs[i]->wperc) {
+                g.push_back(i);
+                placed = true;
+                break;
+            }
+        }
+        if (!placed) work.push_back({i});
+    }
+    auto max_prop = [&](uint32_t i) {
+        int64_t v = 0;
+        for (int64_t x : cfgs[i]->wprop) v = x > v ? x : v;
+        return v;
+    };
+    for (size_t g = 0; g < work.size(); ++g) {  // `work` grows while groups are split
+        for (;;) {
+            if (work[g].size() == 1) {
+                w->dgroups.push_back({work[g], nullptr});
+                break;
+            }
+            const msim_config *f = cfgs[work[g][0]];
+            std::vector<int64_t> pe(f->n, 0);
+            for (uint32_t k = 0; k < f->n; ++k)
+                for (uint32_t i : work[g]) pe[k] = cfgs[i]->wprop[k] > pe[k] ? cfgs[i]->wprop[k] : pe[k];
+            msim_config *env = nullptr;
+            const int rc = wide_copy(f, pe, &env);
+            if (rc) return rc;
+            if (!env->general) {
+                w->dgroups.push_back({work[g], env});
+                break;
+            }
+            delete env;
+            size_t worst = 0;
+            for (size_t j = 1; j < work[g].size(); ++j)
+                if (max_prop(work[g][j]) > max_prop(work[g][worst])) worst = j;
+            const uint32_t pt = work[g][worst];
+            work[g].erase(work[g].begin() + (long)worst);
+            work.push_back({pt});
+        }
+        for (uint32_t i : work[g]) w->group_of[i] = (int32_t)g;
+    }
+    w->shared = true;
+    return MSIM_OK;
+}
+
+// Workspace of a wide sweep: a head with the counters ([0] = 0, [1] = failed (point, run)s over all points), then ONE
+// group region, reused by the groups in turn: a plain wide layout (group of one) or a WideGroupLayout.
+struct WideSweepLayout {
+    size_t group_off, total;
+    uint32_t slice_runs, largest;
+    std::vector<msim::WideLayout> one;       // per group; used when the group has one point
+    std::vector<msim::WideGroupLayout> grp;  // per group; used otherwise
+};
+WideSweepLayout wide_sweep_layout(const msim_sweep *sw, uint64_t rpp)
+{
+    WideSweepLayout l;
+    l.group_off = 256;
+    l.slice_runs = 0;
+    l.largest = 0;
+    size_t gmax = 0;
+    for (const auto &dg : sw->dgroups) {
+        size_t tot;
+        uint32_t nr;
+        if (!dg.env) {
+            l.one.push_back(wide_layout(sw->wcfg[dg.points[0]], rpp));
+            l.grp.emplace_back();
+            tot = l.one.back().total;
+            nr = l.one.back().nr;
+        } else {
+            std::vector<double> rhos;
+            for (uint32_t pt : dg.points) rhos.push_back(sw->rhos[pt]);
+            l.one.emplace_back();
+            l.grp.push_back(msim::wide_group_layout_for(dg.env->rho, rhos, sw->m, dg.env->p.duration_ms, rpp,
+                                                        WIDE_SLICE_BUDGET, max_slice_runs(), wide_test_rcap(false),
+                                                        wide_test_rcap(true)));
+            tot = l.grp.back().total;
+            nr = l.grp.back().nr;
+        }
+        gmax = tot > gmax ? tot : gmax;
+        l.slice_runs = l.slice_runs == 0 || nr < l.slice_runs ? nr : l.slice_runs;
+        l.largest = dg.points.size() > l.largest ? (uint32_t)dg.points.size() : l.largest;
+    }
+    l.total = l.group_off + gmax;
+    return l;
+}
+
+int wide_sweep_launch(msim_sweep *sw, uint64_t run_begin, uint64_t rpp, uint32_t seed_base, void *d_sums, void *d_per_run,
+                      void *d_best_height, void *d_status, char *ws, size_t workspace_bytes, hipStream_t s)
+{
+    using namespace msim;
+    const uint32_t np = (uint32_t)sw->pts.size(), m = sw->m;
+    const WideSweepLayout l = wide_sweep_layout(sw, rpp);
+    if (workspace_bytes < l.total) return MSIM_E_INVALID;
+    // every table first: the rest of the call allocates nothing and does not synchronise
+    std::vector<WideArgs> tabs(sw->dgroups.size());
+    for (size_t g = 0; g < sw->dgroups.size(); ++g) {
+        const auto &dg = sw->dgroups[g];
+        const int rc = wide_tables(dg.env ? dg.env : sw->wcfg[dg.points[0]], &tabs[g]);
+        if (rc) return rc;
+    }
+    const char *pt_tab = nullptr;
+    if (sw->shared) {
+        pt_tab = (const char *)sw->tables.get(TAB_WSPLIT, (size_t)np * m * 12, [&](char *h, const char *) {
+            int64_t *pr = (int64_t *)h;
+            uint32_t *ft = (uint32_t *)(h + (size_t)np * m * 8);
+            for (uint32_t p = 0; p < np; ++p)
+                for (uint32_t k = 0; k < m; ++k) {
+                    pr[(size_t)p * m + k] = sw->wcfg[p]->wprop[k];
+                    ft[(size_t)p * m + k] = wsplit_fthr(sw->wcfg[p]->wprop[k]);
+                }
+        });
+        if (!pt_tab) return MSIM_E_HIP;
+    }
+    uint32_t *counts = (uint32_t *)ws;
+    if (hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), s) != hipSuccess ||
+        hipMemsetAsync(d_sums, 0, 6 * sizeof(uint64_t) * (size_t)m * np, s) != hipSuccess)
+        return MSIM_E_HIP;
+    auto out_of = [&](uint32_t pt) {
+        WideOut o;
+        o.sums = (uint64_t *)d_sums + (size_t)pt * 6 * m;
+        o.records = d_per_run ? (uint32_t *)d_per_run + (size_t)pt * rpp * m * 2 : nullptr;
+        o.best_h = d_best_height ? (uint32_t *)d_best_height + (size_t)pt * rpp : nullptr;
+        o.fail = counts + 1;
+        o.run_begin = run_begin;
+        o.n_total = rpp;
+        o.rel_begin = 0;
+        return o;
+    };
+    for (size_t g = 0; g < sw->dgroups.size(); ++g) {
+        const auto &dg = sw->dgroups[g];
+        WideArgs a = tabs[g];
+        a.seed_base = seed_base;
+        if (!dg.env) {
+            a.rcap = l.one[g].rcap;
+            if (launch_wide(a, l.one[g], ws + l.group_off, out_of(dg.points[0]), s, nullptr) != hipSuccess) return MSIM_E_HIP;
+            continue;
+        }
+        std::vector<WideGroupPoint> pts;
+        for (uint32_t pt : dg.points)
+            pts.push_back(WideGroupPoint{(const int64_t *)pt_tab + (size_t)pt * m,
+                                         (const uint32_t *)(pt_tab + (size_t)np * m * 8) + (size_t)pt * m, out_of(pt)});
+        if (launch_wide_group(a, l.grp[g], pts, ws + l.group_off, run_begin, rpp, s) != hipSuccess) return MSIM_E_HIP;
+    }
+    return hipMemcpyAsync(d_status, counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) == hipSuccess ? MSIM_OK
+                                                                                                             : MSIM_E_HIP;
+}
+
 }  // namespace
 
 void msim::config_weights(const msim_config *cfg, std::vector<uint64_t> *w, uint32_t *total_weight)
@@ -1464,11 +1669,17 @@ int msim_sweep_create_ex(const msim_config *const *cfgs, uint32_t n_points, uint
     w->m = cfgs[0] ? cfgs[0]->n : 0;
     w->self = false;
     bool any_general = false;
-    for (uint32_t i = 0; i < n_points; ++i) any_general = any_general || (cfgs[i] && cfgs[i]->general);
+    bool all_wide = true;  // every point on the large-network pipeline: a wide sweep (msim_widesplit.h)
+    for (uint32_t i = 0; i < n_points; ++i) {
+        any_general = any_general || (cfgs[i] && cfgs[i]->general);
+        all_wide = all_wide && cfgs[i] && cfgs[i]->wide && !cfgs[i]->general;
+    }
     for (uint32_t i = 0; i < n_points; ++i) {
         // one miner count per sweep; narrow networks with percentages unless the sweep runs on the general
-        // engine (the per-lane and entity-engine sweeps share draws and tables between points)
-        if (!cfgs[i] || cfgs[i]->n != w->m || (!any_general && (cfgs[i]->wide || cfgs[i]->total_weight != 100))) {
+        // engine (the per-lane and entity-engine sweeps share draws and tables between points) or every point
+        // runs on the large-network pipeline
+        if (!cfgs[i] || cfgs[i]->n != w->m ||
+            (!any_general && !all_wide && (cfgs[i]->wide || cfgs[i]->total_weight != 100))) {
             delete w;
             return MSIM_E_INVALID;
         }
@@ -1482,6 +1693,12 @@ int msim_sweep_create_ex(const msim_config *const *cfgs, uint32_t n_points, uint
     }
     if (w->general) {  // a point only the general engine serves: every point on G
         w->sel = false;
+    } else if (all_wide) {
+        const int rc = build_wide_groups(w, cfgs, n_points, (flags & MSIM_SWEEP_SHARED_DRAWS) != 0);
+        if (rc) {
+            delete w;
+            return rc;
+        }
     } else if (w->sel) {
         // every point on the entity engine; points grouped by selfish class
         for (uint32_t i = 0; i < n_points; ++i) {
@@ -1547,10 +1764,15 @@ int msim_sweep_info(const msim_sweep *sw, uint64_t runs_per_point, msim_sweep_pl
 {
     if (!sw || !out || runs_per_point == 0 || runs_per_point * sw->pts.size() > msim::MAX_LAUNCH_RUNS) return MSIM_E_INVALID;
     memset(out, 0, sizeof(*out));
-    out->engine = sw->general ? 4u : sw->sel ? 3u : sw->shared ? 1u : 0u;
+    out->engine = sw->general ? 4u : sw->wide ? 2u : sw->sel ? 3u : sw->shared ? 1u : 0u;
     out->slice_runs = (uint32_t)runs_per_point;
     if (sw->sel && !sw->general) out->slice_runs = sel_ws_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point, sw->max_duration).nr;
-    if (sw->shared) {
+    if (sw->wide) {
+        const WideSweepLayout l = wide_sweep_layout(sw, runs_per_point);
+        out->draw_groups = (uint32_t)sw->dgroups.size();
+        out->largest_group = l.largest;
+        out->slice_runs = l.slice_runs;
+    } else if (sw->shared) {
         const SharedLayout l = shared_layout(sw, runs_per_point);
         out->draw_groups = (uint32_t)sw->dgroups.size();
         out->largest_group = l.largest;
@@ -1572,6 +1794,7 @@ size_t msim_sweep_workspace_bytes(const msim_sweep *sw, uint64_t runs_per_point)
 {
     if (!sw || runs_per_point == 0 || runs_per_point * sw->pts.size() > msim::MAX_LAUNCH_RUNS) return 0;
     if (sw->general) return gen_only_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point, sw->max_duration, sw->gen_full).total;
+    if (sw->wide) return wide_sweep_layout(sw, runs_per_point).total;
     if (sw->sel) return sel_ws_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point, sw->max_duration).total;
     if (sw->shared) return shared_layout(sw, runs_per_point).total;
     return sweep_layout(sw->m, (uint32_t)sw->pts.size(), runs_per_point).total;
@@ -1587,6 +1810,9 @@ int msim_sweep_launch(const msim_sweep *sw, uint64_t run_begin, uint64_t runs_pe
     // Stage timing brackets msim_launch only: a sweep launch takes no LaunchTimer and records nothing.
     msim_sweep *sm = const_cast<msim_sweep *>(sw);  // its table cache fills on first use
     const msim::GenParams *gp = nullptr;
+    if (sw->wide)
+        return wide_sweep_launch(sm, run_begin, runs_per_point, seed_base, d_sums, d_per_run, d_best_height, d_status,
+                                 (char *)d_workspace, workspace_bytes, (hipStream_t)stream);
     if (sw->general || sw->sel) {
         std::vector<const GenHost *> hs;
         for (const auto &g : sm->gens) hs.push_back(&g);

@@ -23,6 +23,9 @@
 //                                block's arrival correction, then MinerStats (main.cpp:22-30) for every
 //                                miner into order-independent fixed-point workgroup sums.
 //
+// Sweeps of such networks run W1 once per group of points that share weights and duration, a split kernel WS, then
+// W2 and W3 per point (msim_widesplit.h).
+//
 // PickFinder for integer weights w_k summing to W (W = 100 is exactly the reference's
 // percentages, simulation.h:18,213-221): q = floor(u / MULT), MULT = (2^64-1)/W, finder = first k with
 // cum_k > q. q is p1 = floor(u*W / 2^64) or p1 + 1 (one 64x64 high multiply and one compare, as in

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <map>
 #include <mutex>
@@ -15,6 +16,7 @@
 
 #include "msim_jump.h"
 #include "msim_wide_launch.h"
+#include "msim_widesplit.h"
 
 namespace msim {
 
@@ -247,7 +249,9 @@ __global__ __launch_bounds__(64 * RUNS) __attribute__((amdgpu_waves_per_eu(W1_WA
     wave_sync();
     uint32_t *hout = a.hist + (size_t)r * m;
     for (uint32_t k = lane; k < m; k += 64) hout[k] = s.hist[k];
-    {  // this run's candidate slots on the dense W2 work list (one atomic per run)
+    // this run's candidate slots on the dense W2 work list (one atomic per run); a shared-draw group's envelope
+    // has none (WS builds the points' lists)
+    if (a.work) {
         const uint32_t cc0 = *s.cc, ccn = cc0 < a.rcap ? cc0 : a.rcap;
         uint32_t base = 0;
         if (lane == 0 && ccn) base = atomicAdd(&a.counts[0], ccn);
@@ -268,14 +272,16 @@ __global__ __launch_bounds__(64 * RUNS) __attribute__((amdgpu_waves_per_eu(W1_WA
 // ---------------------------------------------------------------- W2
 // RETRY = false: every candidate with the small capacities (WE_FAST, WA_FAST); an episode that outgrows them is
 // listed for RETRY = true (the record format's WE, WA).
-template <bool RETRY>
-__device__ __forceinline__ void wide_episode_slot(const WideArgs &a, uint32_t slot)
+// SEL (shared-draw groups, msim_widesplit.h): `slot` indexes the point's lists (stride a.rcap = rcap_p); its
+// candidate is the envelope's cand[r * rcap_env + sel[slot]]. a.prop is the point's, a.cf / a.bucket the envelope's.
+template <bool RETRY, bool SEL>
+__device__ __forceinline__ void wide_episode_slot(const WideArgs &a, const WideSel &sl, uint32_t slot)
 {
     const size_t idx = slot;
     const uint32_t r = (uint32_t)(idx / a.rcap);
     const uint32_t *inf = a.info + (size_t)r * 4;
     uint32_t *rec = a.recs + idx * WREC_WORDS;
-    const WideCand e = a.cand[idx];
+    const WideCand e = a.cand[SEL ? (size_t)r * sl.rcap_env + sl.sel[idx] : idx];
     if (inf[3] != 0 || e.block >= inf[0]) {  // failed run, or a block past the end of the run
         rec[0] = e.block + 1;
         rec[1] = WREC_SKIP;
@@ -305,13 +311,23 @@ __device__ __forceinline__ void wide_episode_slot(const WideArgs &a, uint32_t sl
 }
 
 // Grid-stride over the dense lists W1 / the first pass built (every thread of a wave has real work).
-template <bool RETRY>
-__global__ __launch_bounds__(256) void msim_wide_episode_kernel(const WideArgs a)
+template <bool RETRY, bool SEL>
+__device__ __forceinline__ void wide_episode_body(const WideArgs &a, const WideSel &sl)
 {
     const uint32_t total = RETRY ? a.counts[1] : a.counts[0];
     const uint32_t *list = RETRY ? a.retry : a.work;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256)
-        wide_episode_slot<RETRY>(a, list[i]);
+        wide_episode_slot<RETRY, SEL>(a, sl, list[i]);
+}
+template <bool RETRY>
+__global__ __launch_bounds__(256) void msim_wide_episode_kernel(const WideArgs a)
+{
+    wide_episode_body<RETRY, false>(a, WideSel{nullptr, nullptr, 0u});
+}
+template <bool RETRY>
+__global__ __launch_bounds__(256) void msim_wide_episode_sel_kernel(const WideArgs a, const WideSel sl)
+{
+    wide_episode_body<RETRY, true>(a, sl);
 }
 
 // ---------------------------------------------------------------- W3
@@ -332,7 +348,11 @@ __global__ __launch_bounds__(256) void msim_wide_episode_kernel(const WideArgs a
 #endif
 // LDS: acc[m] x {found, stale, share, rate} u64 (workgroup sums), then per wave: hist F[m], stale S[m],
 // sorted candidate keys (block, slot) and their (end, flags), per-(phase, lane) bases.
-__global__ __launch_bounds__(256) void msim_wide_combine_kernel(const WideArgs a, const WideOut out)
+// SEL (shared-draw groups, msim_widesplit.h): the run's candidates are the point's selection sel[r][0..cc) of the
+// envelope's list, already in block order, so the base scan and the sort are skipped; cc = pinfo[r], WIDE_NONE
+// fails the run. hist / info / tlast are the group's shared ones, a.recs / a.rcap / a.prop the point's.
+template <bool SEL>
+__global__ __launch_bounds__(256) void msim_wide_combine_kernel(const WideArgs a, const WideOut out, const WideSel sl)
 {
     extern __shared__ uint64_t sh64[];
     const uint32_t m = a.m, tid = threadIdx.x, w = tid >> 6, lane = tid & 63u;
@@ -352,8 +372,10 @@ __global__ __launch_bounds__(256) void msim_wide_combine_kernel(const WideArgs a
         w3t0 = clock64();
 #endif
         const uint32_t *inf = a.info + (size_t)r * 4;
-        const uint32_t n_end = inf[0], lastf = inf[1], cc = inf[2], rerr = inf[3];
-        bool ok = rerr == 0;
+        const uint32_t n_end = inf[0], lastf = inf[1], rerr = inf[3];
+        const uint32_t pin = SEL ? sl.pinfo[r] : 0u;
+        const uint32_t cc = SEL ? (pin == WIDE_NONE ? 0u : pin) : inf[2];
+        bool ok = SEL ? rerr == 0 && pin != WIDE_NONE : rerr == 0;
         {  // the run's histogram, HB loads per lane in flight together (clamped, unconditional), then stored
             constexpr uint32_t HB = 8;
             const uint32_t *h = a.hist + (size_t)r * m;
@@ -375,7 +397,7 @@ __global__ __launch_bounds__(256) void msim_wide_combine_kernel(const WideArgs a
         const WideLane *lanes = a.lanes + (size_t)r * nph * 64;
         uint32_t run_total = 0;
         constexpr uint32_t PB = 8;  // phases' counts loaded PB at a time (clamped, unconditional)
-        for (uint32_t ph0 = 0; ph0 < nph; ph0 += PB) {
+        for (uint32_t ph0 = 0; ph0 < (SEL ? 0u : nph); ph0 += PB) {
             uint32_t cv[PB];
 #pragma unroll
             for (uint32_t j = 0; j < PB; ++j) cv[j] = lanes[(size_t)(ph0 + j < nph ? ph0 + j : nph - 1) * 64 + lane].count;
@@ -388,10 +410,19 @@ __global__ __launch_bounds__(256) void msim_wide_combine_kernel(const WideArgs a
                 }
             }
         }
-        if (run_total != cc) ok = false;  // overflowed list (also flagged by W1)
+        if (!SEL && run_total != cc) ok = false;  // overflowed list (also flagged by W1)
         wave_sync();
         W3T(1);
-        if (ok) {
+        if constexpr (SEL) {
+            if (ok) {
+                for (uint32_t c = lane; c < cc; c += 64) {
+                    const uint32_t *rec = a.recs + ((size_t)r * a.rcap + c) * WREC_WORDS;
+                    KB[c] = a.cand[(size_t)r * sl.rcap_env + sl.sel[(size_t)r * a.rcap + c]].block;
+                    KE[c] = rec[0];
+                    KF[c] = (rec[1] << 16) | c;
+                }
+            }
+        } else if (ok) {
             for (uint32_t c = lane; c < cc; c += 64) {
                 const WideCand &e = a.cand[(size_t)r * a.rcap + c];
                 const uint32_t pos = base[e.phase * 64 + (e.lane_seq >> 16)] + (e.lane_seq & 0xFFFFu);
@@ -542,6 +573,76 @@ __global__ __launch_bounds__(256) void msim_wide_combine_kernel(const WideArgs a
     }
 }
 
+// ---------------------------------------------------------------- WS (msim_widesplit.h)
+// One wave per run, grid-stride. LDS per wave: the (phase, lane) bases, then the envelope's candidates in block
+// order as two words each (wsplit_pack(slot, finder), I_{s+1}). Then, per point, the entries that pass the point's
+// thresholds go to sel_p[r] in block order (ballot + prefix popcount, 64 entries at a time), the count to
+// pinfo_p[r], and the run's slots to the point's W2 work list.
+__global__ __launch_bounds__(256) void msim_wide_split_kernel(const WideSplitArgs a)
+{
+    extern __shared__ uint64_t sh64[];
+    const uint32_t tid = threadIdx.x, w = tid >> 6, lane = tid & 63u;
+    const uint32_t nph = 1 + a.nch;
+    const size_t per_wave = (size_t)nph * 64 + 2 * (size_t)a.rcap_env;
+    uint32_t *base = (uint32_t *)sh64 + w * per_wave, *SP = base + (size_t)nph * 64, *SI = SP + a.rcap_env;
+    for (uint32_t r = blockIdx.x * 4 + w; r < a.n; r += gridDim.x * 4) {  // wave-uniform loop
+        const uint32_t *inf = a.info + (size_t)r * 4;
+        const uint32_t cc = inf[2], rerr = inf[3];
+        const WideLane *lanes = a.lanes + (size_t)r * nph * 64;
+        uint32_t run_total = 0;
+        wave_sync();  // the previous run's readers are done with the wave's LDS
+        for (uint32_t ph = 0; ph < nph; ++ph) {
+            const uint32_t cv = lanes[(size_t)ph * 64 + lane].count;
+            const uint32_t ex = (uint32_t)wave_excl_scan(cv, lane);
+            base[ph * 64 + lane] = run_total + ex;
+            run_total += __shfl(ex + cv, 63, 64);
+        }
+        // an error bit of W1 (WERR_CAND when the list overflowed), or a count the list does not hold
+        const bool fail = rerr != 0 || run_total != cc || cc > a.rcap_env;
+        wave_sync();
+        if (!fail) {
+            for (uint32_t c = lane; c < cc; c += 64) {
+                const WideCand &e = a.cand[(size_t)r * a.rcap_env + c];
+                const uint32_t pos = base[e.phase * 64 + (e.lane_seq >> 16)] + (e.lane_seq & 0xFFFFu);
+                if (pos < cc) {
+                    SP[pos] = wsplit_pack(c, e.f);
+                    SI[pos] = e.inext;
+                }
+            }
+        }
+        wave_sync();
+        for (uint32_t p = 0; p < a.np; ++p) {  // wave-uniform
+            const WideSplitPoint &pt = a.pt[p];
+            if (fail) {
+                if (lane == 0) pt.pinfo[r] = WIDE_NONE;
+                continue;
+            }
+            uint32_t n = 0;
+            uint32_t *sel = pt.sel + (size_t)r * pt.rcap;
+            for (uint32_t b0 = 0; b0 < cc; b0 += 64) {
+                const uint32_t i = b0 + lane;
+                const bool valid = i < cc;
+                const uint32_t pk = valid ? SP[i] : 0u, in = valid ? SI[i] : 0u;
+                const bool keep = valid && wsplit_keep(pk, in, pt.fthr);
+                const uint64_t bal = __ballot(keep);
+                const uint32_t j = n + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                if (keep && j < pt.rcap) sel[j] = pk & 0xFFFFu;
+                n += (uint32_t)__popcll(bal);
+            }
+            const bool over = n > pt.rcap;
+            uint32_t wb = 0;
+            if (lane == 0) {
+                pt.pinfo[r] = over ? WIDE_NONE : n;
+                if (!over && n) wb = atomicAdd(pt.count, n);
+            }
+            if (!over) {
+                wb = __shfl(wb, 0, 64);
+                for (uint32_t c = lane; c < n; c += 64) pt.work[wb + c] = r * pt.rcap + c;
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- weighted pick (test surface)
 __global__ void msim_wide_pick_kernel(const uint64_t *__restrict__ cf, const uint16_t *__restrict__ bucket, uint32_t m,
                                       uint32_t W, uint64_t mult, const uint64_t *__restrict__ u, int32_t *__restrict__ out,
@@ -608,8 +709,10 @@ size_t wide_w3_lds(uint32_t m, uint32_t rcap, uint32_t nch)
     return (size_t)4 * m * 8 + 4 * ((size_t)2 * m + 3 * (size_t)rcap + (size_t)(1 + nch) * 64) * 4;
 }
 
-hipError_t launch_wide(const WideArgs &proto, const WideLayout &L, char *ws, const WideOut &out, hipStream_t s,
-                       std::vector<hipEvent_t> *w1_events)
+size_t wide_split_lds(uint32_t rcap_env, uint32_t nch) { return 4 * ((size_t)(1 + nch) * 64 + 2 * (size_t)rcap_env) * 4; }
+
+// Kernels with more than 64 KiB of dynamic LDS.
+static void wide_func_attrs()
 {
     static bool attr_done = false;
     if (!attr_done) {
@@ -617,10 +720,31 @@ hipError_t launch_wide(const WideArgs &proto, const WideLayout &L, char *ws, con
         (void)hipFuncSetAttribute((const void *)msim_wide_draws_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         (void)hipFuncSetAttribute((const void *)msim_wide_draws_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         (void)hipFuncSetAttribute((const void *)msim_wide_draws_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute((const void *)msim_wide_combine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void *)msim_wide_combine_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  160 * 1024);
+        (void)hipFuncSetAttribute((const void *)msim_wide_combine_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  160 * 1024);
+        (void)hipFuncSetAttribute((const void *)msim_wide_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024);
         attr_done = true;
     }
+}
+
+static void launch_w1(uint32_t runs, uint32_t cn, size_t l1, hipStream_t s, const WideArgs &a)
+{
+    const dim3 g1((cn + runs - 1) / runs), b1(64 * runs);
+    switch (runs) {
+    case 1: hipLaunchKernelGGL((msim_wide_draws_kernel<1>), g1, b1, l1, s, a); break;
+    case 2: hipLaunchKernelGGL((msim_wide_draws_kernel<2>), g1, b1, l1, s, a); break;
+    case 4: hipLaunchKernelGGL((msim_wide_draws_kernel<4>), g1, b1, l1, s, a); break;
+    default: hipLaunchKernelGGL((msim_wide_draws_kernel<8>), g1, b1, l1, s, a); break;
+    }
+}
+
+hipError_t launch_wide(const WideArgs &proto, const WideLayout &L, char *ws, const WideOut &out, hipStream_t s,
+                       std::vector<hipEvent_t> *w1_events)
+{
+    wide_func_attrs();
     WideArgs a = proto;
     a.hist = (uint32_t *)(ws + L.hist_off);
     a.info = (uint32_t *)(ws + L.info_off);
@@ -646,13 +770,7 @@ hipError_t launch_wide(const WideArgs &proto, const WideLayout &L, char *ws, con
             (void)hipEventRecord(eb, s);
         }
         if (hipMemsetAsync(a.counts, 0, 2 * sizeof(uint32_t), s) != hipSuccess) return hipErrorUnknown;
-        const dim3 g1((cn + runs - 1) / runs), b1(64 * runs);
-        switch (runs) {
-        case 1: hipLaunchKernelGGL((msim_wide_draws_kernel<1>), g1, b1, l1, s, a); break;
-        case 2: hipLaunchKernelGGL((msim_wide_draws_kernel<2>), g1, b1, l1, s, a); break;
-        case 4: hipLaunchKernelGGL((msim_wide_draws_kernel<4>), g1, b1, l1, s, a); break;
-        default: hipLaunchKernelGGL((msim_wide_draws_kernel<8>), g1, b1, l1, s, a); break;
-        }
+        launch_w1(runs, cn, l1, s, a);
         if (ee) (void)hipEventRecord(ee, s);
         // W2 grid: ~rho * blocks candidates per run, grid-stride beyond 16 384 workgroups
         const double est = (double)cn * a.rcap * 0.6;
@@ -663,7 +781,78 @@ hipError_t launch_wide(const WideArgs &proto, const WideLayout &L, char *ws, con
         o.rel_begin = (uint32_t)off;
         uint32_t g3 = (cn + 3) / 4;
         if (g3 > 4096) g3 = 4096;
-        hipLaunchKernelGGL(msim_wide_combine_kernel, dim3(g3), dim3(256), l3, s, a, o);
+        hipLaunchKernelGGL(msim_wide_combine_kernel<false>, dim3(g3), dim3(256), l3, s, a, o, WideSel{nullptr, nullptr, 0u});
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_wide_group(const WideArgs &proto, const WideGroupLayout &L, const std::vector<WideGroupPoint> &pts,
+                             char *ws, uint64_t run_begin, uint64_t n_total, hipStream_t s)
+{
+    wide_func_attrs();
+    const uint32_t np = (uint32_t)pts.size();
+    if (np == 0 || np != L.rcap.size()) return hipErrorInvalidValue;
+    WideArgs a = proto;  // the envelope's draw pass
+    a.rcap = L.rcap_env;
+    a.hist = (uint32_t *)(ws + L.hist_off);
+    a.info = (uint32_t *)(ws + L.info_off);
+    a.tlast = (int64_t *)(ws + L.tlast_off);
+    a.lanes = (WideLane *)(ws + L.lanes_off);
+    a.cand = (WideCand *)(ws + L.cand_off);
+    a.recs = nullptr;
+    a.work = nullptr;
+    a.retry = nullptr;
+    uint32_t *counts = (uint32_t *)(ws + L.counts_off);  // [0..1] the envelope's (unused), then [2] per point
+    a.counts = counts;
+    const uint32_t runs = wide_w1_runs(a.m);
+    const size_t l1 = wide_w1_lds(a.m, runs), ls = wide_split_lds(L.rcap_env, a.nch);
+    if (l1 > 150 * 1024 || ls > 160 * 1024) return hipErrorInvalidValue;
+    for (uint32_t i = 0; i < np; ++i)
+        if (wide_w3_lds(a.m, L.rcap[i], a.nch) > 160 * 1024) return hipErrorInvalidValue;
+    for (uint64_t off = 0; off < n_total; off += L.nr) {
+        const uint32_t cn = (uint32_t)((n_total - off) < L.nr ? (n_total - off) : L.nr);
+        a.run_begin = run_begin + off;
+        a.n = cn;
+        if (hipMemsetAsync(counts, 0, (1 + (size_t)np) * 2 * sizeof(uint32_t), s) != hipSuccess) return hipErrorUnknown;
+        launch_w1(runs, cn, l1, s, a);
+        uint32_t g3 = (cn + 3) / 4;
+        if (g3 > 4096) g3 = 4096;
+        for (uint32_t i0 = 0; i0 < np; i0 += WSPLIT_MAX_POINTS) {
+            WideSplitArgs sa;
+            memset(&sa, 0, sizeof(sa));
+            sa.info = a.info;
+            sa.lanes = a.lanes;
+            sa.cand = a.cand;
+            sa.n = cn;
+            sa.nch = a.nch;
+            sa.rcap_env = L.rcap_env;
+            sa.np = np - i0 < WSPLIT_MAX_POINTS ? np - i0 : WSPLIT_MAX_POINTS;
+            for (uint32_t i = 0; i < sa.np; ++i) {
+                const uint32_t p = i0 + i;
+                sa.pt[i] = WideSplitPoint{pts[p].fthr, (uint32_t *)(ws + L.sel_off[p]), (uint32_t *)(ws + L.pinfo_off[p]),
+                                          (uint32_t *)(ws + L.work_off[p]), counts + 2 * (1 + p), L.rcap[p], 0u};
+            }
+            hipLaunchKernelGGL(msim_wide_split_kernel, dim3(g3), dim3(256), ls, s, sa);
+        }
+        for (uint32_t p = 0; p < np; ++p) {
+            WideArgs b = a;  // the shared draw-side arrays and the envelope's pick tables; the point's delays and lists
+            b.prop = pts[p].prop;
+            b.rcap = L.rcap[p];
+            b.recs = (uint32_t *)(ws + L.recs_off[p]);
+            b.work = (uint32_t *)(ws + L.work_off[p]);
+            b.retry = (uint32_t *)(ws + L.retry_off[p]);
+            b.counts = counts + 2 * (1 + p);
+            const WideSel sl{(const uint32_t *)(ws + L.sel_off[p]), (const uint32_t *)(ws + L.pinfo_off[p]), L.rcap_env};
+            const double est = (double)cn * b.rcap * 0.6;
+            const unsigned g2 = (unsigned)(est / 256 < 16384 ? est / 256 + 1 : 16384);
+            hipLaunchKernelGGL(msim_wide_episode_sel_kernel<false>, dim3(g2), dim3(256), 0, s, b, sl);
+            hipLaunchKernelGGL(msim_wide_episode_sel_kernel<true>, dim3(64), dim3(256), 0, s, b, sl);
+            WideOut o = pts[p].out;
+            o.rel_begin = (uint32_t)off;
+            hipLaunchKernelGGL(msim_wide_combine_kernel<true>, dim3(g3), dim3(256), wide_w3_lds(a.m, b.rcap, a.nch), s, b, o, sl);
+        }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

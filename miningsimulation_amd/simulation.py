@@ -352,11 +352,17 @@ class Sweep:
     shared_draws=True asks for the shared-draw form (msim_sweep_create_ex, MSIM_SWEEP_SHARED_DRAWS): honest points
     with the same weights share ONE draw pass per slice; only the short per-point tails run per point. Same
     results, bit for bit; a sweep the form does not serve (a selfish point, a delay the pipeline does not take)
-    runs as without it. plan() tells which engine serves the sweep."""
+    runs as without it. plan() tells which engine serves the sweep.
+
+    total_weight != 100 (Miner.perc are integer weights summing to it) or more than 15 honest miners: every point
+    runs on the large-network pipeline (engine 2). Without shared_draws each point is a plain launch of that
+    pipeline; with it, points with equal weights share one draw pass on the group's envelope network (every miner
+    at its largest delay over the group). The shared form can fail a run (MSIM_E_CAPACITY) that the point's own
+    launch would not, but only when the ENVELOPE's candidate list overflows (an 8-sigma event)."""
 
     def __init__(self, points: Sequence[Sequence[Miner]], duration_ms: int = SIM_DURATION_MS,
-                 shared_draws: bool = False):
-        self.sims = [Simulation(p, duration_ms) for p in points]
+                 shared_draws: bool = False, total_weight: int = 100):
+        self.sims = [Simulation(p, duration_ms, total_weight) for p in points]
         self.m = len(self.sims[0].miners)
         handles = (ctypes.c_void_p * len(self.sims))(*[s.handle.value for s in self.sims])
         h = ctypes.c_void_p()
@@ -365,8 +371,10 @@ class Sweep:
         self._h = h
 
     def plan(self, runs_per_point: int) -> dict:
-        """msim_sweep_info: engine (0 per-lane kernel, 1 shared-draw pipeline, 3 entity engine, 4 general engine),
-        draw_groups, largest_group, slice_runs, workspace_bytes. Host only."""
+        """msim_sweep_info: engine (0 per-lane kernel, 1 shared-draw pipeline, 2 large-network pipeline, 3 entity
+        engine, 4 general engine), draw_groups, largest_group, slice_runs, workspace_bytes. For engine 2 draw_groups
+        counts every group (without shared_draws: one per point) and slice_runs is the smallest group's slice.
+        Host only."""
         pl = MsimSweepPlan()
         check(lib.msim_sweep_info(self._h, runs_per_point, ctypes.byref(pl)), "msim_sweep_info")
         return {f: int(getattr(pl, f)) for f, _ in MsimSweepPlan._fields_}
@@ -464,13 +472,15 @@ class Sweep:
                                     d_workspace.numel(), sh), "msim_sweep_launch")
 
 
-def propagation_sweep(miners: Sequence[Miner], delays_ms: Sequence[int], duration_ms: int = SIM_DURATION_MS) -> Sweep:
+def propagation_sweep(miners: Sequence[Miner], delays_ms: Sequence[int], duration_ms: int = SIM_DURATION_MS,
+                      total_weight: int = 100) -> Sweep:
     """One network at several uniform propagation delays (the reference's first example, README.md:21-27: the
     same hashrates at 10 s and at 100 ms, one rebuild each) as a shared-draw sweep: point i is `miners` with every
     propagation_ms = delays_ms[i]. All points share their draws, so run_contrasts(..., pairs_vs_baseline(...))
-    gives the differences between delays with the per-run difference's error."""
+    gives the differences between delays with the per-run difference's error. Large networks (c5_network() with
+    total_weight=C5_TOTAL_WEIGHT) take the large-network pipeline's shared form."""
     points = [[Miner(mn.id, mn.perc, int(d), mn.is_selfish) for mn in miners] for d in delays_ms]
-    return Sweep(points, duration_ms, shared_draws=True)
+    return Sweep(points, duration_ms, shared_draws=True, total_weight=total_weight)
 
 
 def timing_enable(on: bool = True) -> None:
