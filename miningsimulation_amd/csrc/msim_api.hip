@@ -11,11 +11,13 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <vector>
 
 #include "../../include/msim.h"
 #include "msim_devcache.h"
+#include "msim_drawgroups.h"
 #include "msim_general_launch.h"
 #include "msim_host.h"
 #include "msim_jump.h"
@@ -264,7 +266,7 @@ msim::PipeLayout pipe_layout(const msim_config *c, uint64_t n_runs)
     uint32_t slots = jobs == 1u ? draw_slots() * 3u : draw_slots() * 2u / jobs;
     if (slots < 1u) slots = 1u;
     const msim::PipeLimits lim = pipe_test_limits(false);
-    const msim::PipeLayout L = msim::pipe_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, PIPE_SLICE_BUDGET, slots, 0.0, lim);
+    const msim::PipeLayout L = msim::pipe_layout_for(c->rho, c->n, c->p.duration_ms, n_runs, PIPE_SLICE_BUDGET, slots, lim);
     const uint32_t cap = max_slice_runs();  // the layout of a slice of exactly `cap` runs, not a smaller budget's
     return cap && L.nr > cap ? msim::pipe_layout_nr(c->rho, c->n, c->p.duration_ms, cap, slots, lim) : L;
 }
@@ -480,12 +482,8 @@ uint32_t seg_max_nr(uint32_t m, double rate, int64_t duration_ms, uint64_t n_run
 {
     uint64_t nr = align256(n_runs);
     if (nr > (1u << 22)) nr = 1u << 22;
-    for (;;) {  // the geometry depends on the slice size: shrink until one slice's records fit the budget
-        const SegLayout L = seg_layout_nr(m, rate, duration_ms, (uint32_t)nr);
-        if ((double)L.total <= SEG_BUDGET || nr <= 256) return (uint32_t)nr;
-        uint64_t next = (uint64_t)((double)nr * SEG_BUDGET / (double)L.total * 0.98) / 256 * 256;
-        nr = next >= nr ? nr - 256 : (next < 256 ? 256 : next);
-    }
+    // the geometry depends on the slice size: shrink until one slice's records fit the budget
+    return msim::fit_slice(nr, SEG_BUDGET, [&](uint32_t n) { return seg_layout_nr(m, rate, duration_ms, n); }).nr;
 }
 
 // The E1 workspace of a single-network launch, plus the segment-parallel form's records when it serves the config.
@@ -912,50 +910,40 @@ int launch_wide_cfg(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs,
 // the largest delay to a group of its own until it does. A group of one is the plain pipeline on that point.
 int build_draw_groups(msim_sweep *w, const msim_config *const *cfgs, uint32_t np)
 {
-    std::vector<std::vector<uint32_t>> work;
-    for (uint32_t i = 0; i < np; ++i) {
-        bool placed = false;
-        for (auto &g : work) {
-            const msim_config *f = cfgs[g[0]];
-            if (f->p.duration_ms == cfgs[i]->p.duration_ms && !memcmp(f->perc, cfgs[i]->perc, sizeof(uint64_t) * f->n)) {
-                g.push_back(i);
-                placed = true;
-                break;
-            }
+    auto envelope = [&](const std::vector<uint32_t> &points, msim_config **env) {
+        const msim_config *f = cfgs[points[0]];
+        std::vector<msim_miner> ms(f->n);
+        for (uint32_t k = 0; k < f->n; ++k) {
+            int64_t pe = 0;
+            for (uint32_t i : points) pe = cfgs[i]->prop[k] > pe ? cfgs[i]->prop[k] : pe;
+            ms[k] = msim_miner{f->ids[k], f->perc[k], pe, 0};
         }
-        if (!placed) work.push_back({i});
-    }
-    auto max_prop = [&](uint32_t i) {
-        int64_t v = 0;
-        for (uint32_t k = 0; k < cfgs[i]->n; ++k) v = cfgs[i]->prop[k] > v ? cfgs[i]->prop[k] : v;
-        return v;
+        return config_create_impl(ms.data(), f->n, f->p.duration_ms, 100u, env);
     };
-    w->group_of.assign(np, -1);
-    for (size_t g = 0; g < work.size(); ++g) {  // `work` grows while groups are split
-        for (;;) {
-            const msim_config *f = cfgs[work[g][0]];
-            std::vector<msim_miner> ms(f->n);
-            for (uint32_t k = 0; k < f->n; ++k) {
-                int64_t pe = 0;
-                for (uint32_t i : work[g]) pe = cfgs[i]->prop[k] > pe ? cfgs[i]->prop[k] : pe;
-                ms[k] = msim_miner{f->ids[k], f->perc[k], pe, 0};
-            }
+    std::vector<std::vector<uint32_t>> groups;
+    std::vector<std::unique_ptr<msim_config>> taken;  // the envelopes of the groups of two or more, in group order
+    int rc = msim::plan_draw_groups(
+        np,
+        [&](uint32_t i, uint32_t j) {
+            return cfgs[i]->p.duration_ms == cfgs[j]->p.duration_ms &&
+                   !memcmp(cfgs[i]->perc, cfgs[j]->perc, sizeof(uint64_t) * cfgs[i]->n);
+        },
+        [&](uint32_t i) { return *std::max_element(cfgs[i]->prop, cfgs[i]->prop + cfgs[i]->n); },
+        [&](const std::vector<uint32_t> &points, bool *ok) {
             msim_config *env = nullptr;
-            const int rc = config_create_impl(ms.data(), f->n, f->p.duration_ms, 100u, &env);
-            if (rc) return rc;
-            if (env->pipe_ok || work[g].size() == 1) {
-                w->dgroups.push_back({work[g], env});
-                break;
-            }
-            delete env;
-            size_t worst = 0;
-            for (size_t j = 1; j < work[g].size(); ++j)
-                if (max_prop(work[g][j]) > max_prop(work[g][worst])) worst = j;
-            const uint32_t pt = work[g][worst];
-            work[g].erase(work[g].begin() + (long)worst);
-            work.push_back({pt});
-        }
-        for (uint32_t i : work[g]) w->group_of[i] = (int32_t)g;
+            const int rc = envelope(points, &env);
+            *ok = rc == MSIM_OK && env->pipe_ok;
+            if (*ok) taken.emplace_back(env);
+            else delete env;
+            return rc;
+        },
+        &groups, &w->group_of);
+    if (rc) return rc;
+    for (size_t g = 0, t = 0; g < groups.size(); ++g) {
+        msim_config *env = nullptr;
+        if (groups[g].size() > 1) env = taken[t++].release();
+        else if ((rc = envelope(groups[g], &env)) != MSIM_OK) return rc;  // the point's own delays, whatever the pipeline says
+        w->dgroups.push_back({groups[g], env});
     }
     for (uint32_t i = 0; i < np; ++i) w->rhos.push_back(cfgs[i]->rho);
     w->shared = true;
@@ -1020,13 +1008,7 @@ SharedGroupLayout shared_group_layout(const msim_sweep *sw, const msim_sweep::Dr
     uint64_t nr = (rpp + 255) / 256 * 256;
     const uint32_t cap = max_slice_runs();
     if (cap && nr > cap) nr = cap;
-    for (;;) {
-        SharedGroupLayout L = shared_group_nr(sw, dg, (uint32_t)nr, slots);
-        if ((double)L.total <= PIPE_SLICE_BUDGET || nr <= 256) return L;
-        uint64_t next = (uint64_t)((double)nr * PIPE_SLICE_BUDGET / (double)L.total * 0.98) / 256 * 256;
-        if (next >= nr) next = nr - 256;
-        nr = next < 256 ? 256 : next;
-    }
+    return msim::fit_slice(nr, PIPE_SLICE_BUDGET, [&](uint32_t n) { return shared_group_nr(sw, dg, n, slots); });
 }
 
 SharedLayout shared_layout(const msim_sweep *sw, uint64_t rpp)
@@ -1084,27 +1066,8 @@ int shared_launch_impl(msim_sweep *sw, uint64_t run_begin, uint64_t rpp, uint32_
         const PipeLayout &L = G.env;
         const uint32_t ng = (uint32_t)dg.points.size();
         char *gw = ws + l.group_off;
-        DrawArgs da;
-        da.tab = tabs[g];
+        DrawArgs da = draw_args(L, gw, tabs[g]);
         da.seed_base = seed_base;
-        da.nr = L.nr;
-        da.seg = L.seg;
-        da.gps = L.gps;
-        da.nseg = L.nseg;
-        da.cap = L.cap;
-        da.band_lo = L.band_lo;
-        da.lcap = L.lcap;
-        da.lchunk = L.lchunk;
-        da.segsum = (uint64_t *)(gw + L.segsum_off);
-        da.segcnt = (uint32_t *)(gw + L.segcnt_off);
-        da.nslow = (uint32_t *)(gw + L.nslow_off);
-        da.slots = (uint32_t *)(gw + L.slots_off);
-        da.gsum = (uint32_t *)(gw + L.gsum_off);
-        da.gend = (uint64_t *)(gw + L.gend_off);
-        da.gcum = (uint32_t *)(gw + L.gcum_off);
-        da.grec = (GroupRec *)(gw + L.grec_off);
-        da.list = (EpEntry *)(gw + L.list_off);
-        da.list_count = (uint32_t *)(gw + L.count_off);
         std::vector<LaunchArgs> las(ng);
         std::vector<PipeArgs> pas(ng);
         std::vector<uint32_t *> sels(ng);  // sel_p
@@ -1133,25 +1096,12 @@ int shared_launch_impl(msim_sweep *sw, uint64_t run_begin, uint64_t rpp, uint32_
             a.tab = tabs[g];
             a.k1_events = nullptr;
             PipeArgs &pa = pas[i];
-            pa.nr = L.nr;
-            pa.seg = L.seg;
-            pa.gps = L.gps;
-            pa.nseg = L.nseg;
-            pa.nb = L.nb;
+            pa = pipe_args(L, gw, tabs[g]);  // K2 and K3 read only the finder of a pick entry: the envelope's tables serve every point
             pa.cap = P.cap;
-            pa.band_lo = L.band_lo;
             pa.lcap = P.lcap;
             pa.rec_words = P.rec_words;
-            pa.tab = tabs[g];  // K2 and K3 read only the finder of a pick entry: the envelope's tables serve every point
-            pa.segsum = da.segsum;
-            pa.segcnt = da.segcnt;
             pa.nslow = (const uint32_t *)(gw + G.nslow_off[i]);
             pa.slots = (const uint32_t *)(gw + G.slots_off[i]);
-            pa.gsum = da.gsum;
-            pa.gend = da.gend;
-            pa.gcum = da.gcum;
-            pa.grec = da.grec;
-            pa.list = da.list;
             pa.list_count = (const uint32_t *)(gw + G.counts_off) + i;
             pa.recs = (uint32_t *)(gw + G.recs_off[i]);
             sels[i] = (uint32_t *)(gw + G.sel_off[i]);
@@ -1227,52 +1177,31 @@ int build_wide_groups(msim_sweep *w, const msim_config *const *cfgs, uint32_t np
         for (uint32_t i = 0; i < np; ++i) w->dgroups.push_back({{i}, nullptr});
         return MSIM_OK;
     }
-    std::vector<std::vector<uint32_t>> work;
-    for (uint32_t i = 0; i < np; ++i) {
-        bool placed = false;
-        for (auto &g : work) {
-            const msim_config *f = cfgs[g[0]];
-            if (f->p.duration_ms == cfgs[i]->p.duration_ms && f->total_weight == cfgs[i]->total_weight &&
-                f->wperc == cfgs[i]->wperc) {
-                g.push_back(i);
-                placed = true;
-                break;
-            }
-        }
-        if (!placed) work.push_back({i});
-    }
-    auto max_prop = [&](uint32_t i) {
-        int64_t v = 0;
-        for (int64_t x : cfgs[i]->wprop) v = x > v ? x : v;
-        return v;
-    };
-    for (size_t g = 0; g < work.size(); ++g) {  // `work` grows while groups are split
-        for (;;) {
-            if (work[g].size() == 1) {
-                w->dgroups.push_back({work[g], nullptr});
-                break;
-            }
-            const msim_config *f = cfgs[work[g][0]];
+    std::vector<std::vector<uint32_t>> groups;
+    std::vector<std::unique_ptr<msim_config>> taken;  // the envelopes of the groups of two or more, in group order
+    const int rc = msim::plan_draw_groups(
+        np,
+        [&](uint32_t i, uint32_t j) {
+            return cfgs[i]->p.duration_ms == cfgs[j]->p.duration_ms && cfgs[i]->total_weight == cfgs[j]->total_weight &&
+                   cfgs[i]->wperc == cfgs[j]->wperc;
+        },
+        [&](uint32_t i) { return *std::max_element(cfgs[i]->wprop.begin(), cfgs[i]->wprop.end()); },
+        [&](const std::vector<uint32_t> &points, bool *ok) {
+            const msim_config *f = cfgs[points[0]];
             std::vector<int64_t> pe(f->n, 0);
             for (uint32_t k = 0; k < f->n; ++k)
-                for (uint32_t i : work[g]) pe[k] = cfgs[i]->wprop[k] > pe[k] ? cfgs[i]->wprop[k] : pe[k];
+                for (uint32_t i : points) pe[k] = cfgs[i]->wprop[k] > pe[k] ? cfgs[i]->wprop[k] : pe[k];
             msim_config *env = nullptr;
             const int rc = wide_copy(f, pe, &env);
-            if (rc) return rc;
-            if (!env->general) {
-                w->dgroups.push_back({work[g], env});
-                break;
-            }
-            delete env;
-            size_t worst = 0;
-            for (size_t j = 1; j < work[g].size(); ++j)
-                if (max_prop(work[g][j]) > max_prop(work[g][worst])) worst = j;
-            const uint32_t pt = work[g][worst];
-            work[g].erase(work[g].begin() + (long)worst);
-            work.push_back({pt});
-        }
-        for (uint32_t i : work[g]) w->group_of[i] = (int32_t)g;
-    }
+            *ok = rc == MSIM_OK && !env->general;
+            if (*ok) taken.emplace_back(env);
+            else delete env;
+            return rc;
+        },
+        &groups, &w->group_of);
+    if (rc) return rc;
+    size_t t = 0;
+    for (const auto &g : groups) w->dgroups.push_back({g, g.size() > 1 ? taken[t++].release() : nullptr});
     w->shared = true;
     return MSIM_OK;
 }

@@ -278,49 +278,9 @@ static hipError_t launch_pipeline(const LaunchArgs &a, uint64_t *parts)
 {
     const PipeLayout &L = *a.pl;
     char *ws = a.pipe_ws;
-    PipeArgs pa;
-    pa.nr = L.nr;
-    pa.seg = L.seg;
-    pa.gps = L.gps;
-    pa.nseg = L.nseg;
-    pa.nb = L.nb;
-    pa.cap = L.cap;
-    pa.band_lo = L.band_lo;
-    pa.lcap = L.lcap;
-    pa.rec_words = L.rec_words;
-    pa.tab = a.tab;
-    pa.segsum = (const uint64_t *)(ws + L.segsum_off);
-    pa.segcnt = (const uint32_t *)(ws + L.segcnt_off);
-    pa.nslow = (const uint32_t *)(ws + L.nslow_off);
-    pa.slots = (const uint32_t *)(ws + L.slots_off);
-    pa.gsum = (const uint32_t *)(ws + L.gsum_off);
-    pa.gend = (const uint64_t *)(ws + L.gend_off);
-    pa.gcum = (const uint32_t *)(ws + L.gcum_off);
-    pa.grec = (const GroupRec *)(ws + L.grec_off);
-    pa.list = (const EpEntry *)(ws + L.list_off);
-    pa.list_count = (const uint32_t *)(ws + L.count_off);
-    pa.recs = (uint32_t *)(ws + L.recs_off);
-    DrawArgs da;
-    da.tab = a.tab;
+    const PipeArgs pa = pipe_args(L, ws, a.tab);
+    DrawArgs da = draw_args(L, ws, a.tab);
     da.seed_base = a.seed_base;
-    da.nr = L.nr;
-    da.seg = L.seg;
-    da.gps = L.gps;
-    da.nseg = L.nseg;
-    da.cap = L.cap;
-    da.band_lo = L.band_lo;
-    da.lcap = L.lcap;
-    da.lchunk = L.lchunk;
-    da.segsum = (uint64_t *)(ws + L.segsum_off);
-    da.segcnt = (uint32_t *)(ws + L.segcnt_off);
-    da.nslow = (uint32_t *)(ws + L.nslow_off);
-    da.slots = (uint32_t *)(ws + L.slots_off);
-    da.gsum = (uint32_t *)(ws + L.gsum_off);
-    da.gend = (uint64_t *)(ws + L.gend_off);
-    da.gcum = (uint32_t *)(ws + L.gcum_off);
-    da.grec = (GroupRec *)(ws + L.grec_off);
-    da.list = (EpEntry *)(ws + L.list_off);
-    da.list_count = (uint32_t *)(ws + L.count_off);
     // Test switch (MSIM_PIPE_FORCE_RETRY, the pipeline's MSIM_SEL_FORCE_RETRY): K3 is given a band that begins past
     // the last segment, so combine_run flags every run at its first check (the run ends before the band) and the
     // retry kernel computes them all. The pipeline's own retries need an 8-sigma event, so nothing else sends the

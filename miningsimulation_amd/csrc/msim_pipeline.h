@@ -253,19 +253,82 @@ inline PipeLayout pipe_layout_nr(double rho, uint32_t m, int64_t duration_ms, ui
     return pipe_layout_w(rho, m, duration_ms, nr, pipe_workers(duration_ms, nr, slots), lim);
 }
 
-// The largest slice (all n_runs, or fewer) whose layout, plus extra_per_run bytes per run, fits the budget.
-inline PipeLayout pipe_layout_for(double rho, uint32_t m, int64_t duration_ms, uint64_t n_runs, double budget,
-                                  uint32_t slots, double extra_per_run = 0.0, const PipeLimits &lim = PipeLimits())
+// The layout of the largest slice, `nr` runs (a multiple of 256) or fewer, whose `total` bytes fit the budget. A layout's
+// geometry depends on its slice size, so it shrinks in steps: by the excess and 2 % more, to whole 256s, at least 256
+// at a time, not below 256. layout_at(nr) is computed once per step and the last one is returned.
+template <class LayoutAt>
+inline auto fit_slice(uint64_t nr, double budget, LayoutAt layout_at) -> decltype(layout_at(0u))
 {
-    uint64_t nr = (n_runs + 255) / 256 * 256;
     for (;;) {
-        const PipeLayout L = pipe_layout_nr(rho, m, duration_ms, (uint32_t)nr, slots, lim);
-        const double tot = (double)L.total + extra_per_run * (double)nr;
-        if (tot <= budget || nr <= 256) return L;
-        uint64_t next = (uint64_t)((double)nr * budget / tot * 0.98) / 256 * 256;
+        const auto L = layout_at((uint32_t)nr);
+        if ((double)L.total <= budget || nr <= 256) return L;
+        uint64_t next = (uint64_t)((double)nr * budget / (double)L.total * 0.98) / 256 * 256;
         if (next >= nr) next = nr - 256;
         nr = next < 256 ? 256 : next;
     }
+}
+
+// The largest slice (all n_runs, or fewer) whose layout fits the budget.
+inline PipeLayout pipe_layout_for(double rho, uint32_t m, int64_t duration_ms, uint64_t n_runs, double budget,
+                                  uint32_t slots, const PipeLimits &lim = PipeLimits())
+{
+    return fit_slice((n_runs + 255) / 256 * 256, budget,
+                     [&](uint32_t nr) { return pipe_layout_nr(rho, m, duration_ms, nr, slots, lim); });
+}
+
+// The launch arguments a layout determines, for a slice region at `ws`: every field but run_begin, n and seed_base,
+// which the caller sets per slice and launch.
+inline DrawArgs draw_args(const PipeLayout &L, char *ws, const PipeTables &tab)
+{
+    DrawArgs a = {};
+    a.tab = tab;
+    a.nr = L.nr;
+    a.seg = L.seg;
+    a.gps = L.gps;
+    a.nseg = L.nseg;
+    a.cap = L.cap;
+    a.band_lo = L.band_lo;
+    a.lcap = L.lcap;
+    a.lchunk = L.lchunk;
+    a.segsum = (uint64_t *)(ws + L.segsum_off);
+    a.segcnt = (uint32_t *)(ws + L.segcnt_off);
+    a.nslow = (uint32_t *)(ws + L.nslow_off);
+    a.slots = (uint32_t *)(ws + L.slots_off);
+    a.gsum = (uint32_t *)(ws + L.gsum_off);
+    a.gend = (uint64_t *)(ws + L.gend_off);
+    a.gcum = (uint32_t *)(ws + L.gcum_off);
+    a.grec = (GroupRec *)(ws + L.grec_off);
+    a.list = (EpEntry *)(ws + L.list_off);
+    a.list_count = (uint32_t *)(ws + L.count_off);
+    return a;
+}
+
+inline PipeArgs pipe_args(const PipeLayout &L, char *ws, const PipeTables &tab)
+{
+    const DrawArgs d = draw_args(L, ws, tab);  // K2 and K3 read what K1 wrote
+    PipeArgs a = {};
+    a.nr = L.nr;
+    a.seg = L.seg;
+    a.gps = L.gps;
+    a.nseg = L.nseg;
+    a.nb = L.nb;
+    a.cap = L.cap;
+    a.band_lo = L.band_lo;
+    a.lcap = L.lcap;
+    a.rec_words = L.rec_words;
+    a.tab = tab;
+    a.segsum = d.segsum;
+    a.segcnt = d.segcnt;
+    a.nslow = d.nslow;
+    a.slots = d.slots;
+    a.gsum = d.gsum;
+    a.gend = d.gend;
+    a.gcum = d.gcum;
+    a.grec = d.grec;
+    a.list = d.list;
+    a.list_count = d.list_count;
+    a.recs = (uint32_t *)(ws + L.recs_off);
+    return a;
 }
 
 // ---------------------------------------------------------------- K1 lane body (shared host/device)
