@@ -144,7 +144,9 @@ struct DevCtx {
 // VALU instructions per block; profiles/r07/INDEX.md): 4 waves (102 VGPRs, no scratch) 11.40 M run-years/s serial
 // and 12.41 M on two streams, 5 (96, 8 spills) 11.38 M / 12.32 M, 6 (80) 11.01 M / 12.48 M: 4 is the only budget
 // that is at or near the top of both lines. Round 8's loop spends the slack of that budget on values held across the
-// loop (DevCtx::hold, K1Draws::begin): 105 VGPRs, no scratch (profiles/r08/INDEX.md).
+// loop (DevCtx::hold, K1Draws::begin): 105 VGPRs, no scratch (profiles/r08/INDEX.md). Round 12's quad (one 64-bit
+// shift in the state update, the picker by one multiply, v without conversions) needs 96, still at this budget
+// (profiles/r12/INDEX.md).
 #ifndef MSIM_K1_WAVES
 #define MSIM_K1_WAVES 4
 #endif

@@ -81,8 +81,20 @@ __device__ __forceinline__ uint64_t add64(uint64_t a, uint64_t b)
     asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// x << 21 as ONE v_lshlrev_b64. Written as plain C++, LLVM splits the shift into v_lshlrev_b32 (low half) and
+// v_alignbit_b32 (high half): two instructions of the slow issue class (scripts/ubench/valu_rates.hip) where
+// one of the same class does.
+__device__ __forceinline__ uint64_t shl21(uint64_t x)
+{
+    uint64_t r;
+    asm("v_lshlrev_b64 %0, 21, %1" : "=v"(r) : "v"(x));
+    return r;
+}
 #endif
 
+// SHL64 (device only; the value is the same): s1 << 21 by shl21. The draw kernel's quad asks for it
+// (msim_pipeline.h k1p_quad_fast); every other caller keeps the compiler's form, and its code as it was.
+template <bool SHL64 = false>
 MSIM_HD uint64_t rng_next(Rng &r)  // xoroshiro128++.h:26-34
 {
     const uint64_t s0 = r.s0;
@@ -91,7 +103,7 @@ MSIM_HD uint64_t rng_next(Rng &r)  // xoroshiro128++.h:26-34
     const uint64_t result = add64(rotl64(s0 + s1, 17), s0);
     s1 ^= s0;
     // s0' = rotl(s0, 49) ^ s1 ^ (s1 << 21): one three-input XOR per half (v_bitop3_b32, table 0x96)
-    const uint64_t ro = rotl64(s0, 49), sh = s1 << 21;
+    const uint64_t ro = rotl64(s0, 49), sh = SHL64 ? shl21(s1) : s1 << 21;
     const uint32_t lo = __builtin_amdgcn_bitop3_b32((uint32_t)ro, (uint32_t)s1, (uint32_t)sh, 0x96);
     const uint32_t hi = __builtin_amdgcn_bitop3_b32((uint32_t)(ro >> 32), (uint32_t)(s1 >> 32), (uint32_t)(sh >> 32), 0x96);
     r.s0 = ((uint64_t)hi << 32) | lo;

@@ -328,14 +328,36 @@ MSIM_HD int32_t k1_interval_general(uint64_t u, const K1Log *__restrict__ tab, b
 //   two-sided test, the per-draw rebase of the key (v_add_u32) goes, and the quad's max runs on the raw high
 //   words. The lower margin is now M itself (the folded form asks one high-word step more), the upper one
 //   1 - 6 * 2^-21 - M = 1.61 ns; rejected share 2^-15 + 2.86e-6.
+// v without conversions: the general form builds v = 1 - (u>>11) 2^-53 from two v_cvt_f64_u32 and two FMAs. The
+//   packed form writes each 32-bit half of the draw into the low word of a double whose high word is a constant,
+//   which IS an exact double, and subtracts twice:
+//     dh = [K1V_HI_WORD : hi]       = 2^20 + hi 2^-32        (exponent 2^20: one unit in the last place is 2^-32)
+//     dl = [K1V_LO_WORD : lo >> 11] = 1/2 + (lo >> 11) 2^-53 (exponent 2^-1: one unit is 2^-53; lo >> 11 < 2^21)
+//     c  = K1V_BASE - dh = 1.5 - hi 2^-32      a multiple of 2^-32 in (0.5, 1.5]: representable, so the
+//                                              subtraction rounds to it exactly
+//     v  = c - dl        = 1 - (u>>11) 2^-53   a multiple of 2^-53 in (0, 1]: representable, exact
+//   so v has the bits of the general form's v for every u (tests/native/k1v_check.cpp). Both conversions, of the
+//   slow issue class, go; in their place the quad has two v_mov_b32 per draw (a half, or a high word, into its
+//   pair), of the cheap class: the compiler keeps one copy of each high word in a register across the loop and
+//   writes lo >> 11 of every other draw straight beside it, and K1V_BASE is a scalar addend. The instruction
+//   count is unchanged and K1 is 4.8 % faster (profiles/r12/INDEX.md). Two held copies of each high word (one per
+//   draw in flight, four moves a quad fewer, 100 VGPRs) measured 0.4 % SLOWER and were not kept.
+constexpr uint32_t K1V_HI_WORD = 0x41300000u, K1V_LO_WORD = 0x3FE00000u;
+constexpr double K1V_BASE = 0x1.0p20 + 1.5;
+MSIM_HD double k1p_v(uint64_t u)
+{
+    const uint32_t lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
+    const double dh = __builtin_bit_cast(double, ((uint64_t)K1V_HI_WORD << 32) | hi);
+    const double dl = __builtin_bit_cast(double, ((uint64_t)K1V_LO_WORD << 32) | (lo >> 11));
+    const double c = K1V_BASE - dh;
+    return c - dl;
+}
 constexpr uint32_t K1P_OK_HI = 0x3FEFFFFAu;  // hi(1 - 2.5e-6) (exclusive)
 constexpr uint32_t K1P_VH_MIN = (uint32_t)(1023 - (K1_EROWS - 1)) << 20;  // high word of 2^-15
 // z - M of the packed form; vh = the high word of v, r = the polynomial's argument.
 MSIM_HD double k1p_interval_z(uint64_t u, const K1Pair *__restrict__ P, uint32_t &vh, double &r, FdConsts kc = MSIM_K1_CONSTS)
 {
-    const uint32_t lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
-    const double c = __builtin_fma(u32_to_f64(lo >> 11), -0x1.0p-53, 1.0);  // exact
-    const double v = __builtin_fma(u32_to_f64(hi), -0x1.0p-32, c);           // exact: 1 - (u>>11) 2^-53
+    const double v = k1p_v(u);
     vh = (uint32_t)(__builtin_bit_cast(uint64_t, v) >> 32);
     const uint32_t off = (vh >> (FD_VT_SHIFT + 3 - 4)) & ((K1_EROWS * LOG_TAB - 1u) << 4);
     const K1Pair en = *(const K1Pair *)((const char *)P + off);
@@ -417,15 +439,38 @@ MSIM_HD uint32_t pick_info(uint64_t u, const PickTab *__restrict__ tab)
 // 100 (h' + 1) = p 2^32 + key + 100 with key + 100 < 2^32 - 156, so h' + 1 has the same p and its low word is
 // below PICK_RARE_LO: q = p for either carry. (h' = 2^32 - 1, whose successor wraps, has key = 2^32 - 100: rare.)
 // A key at or above the band (6e-8 of draws) sends the quad to pick_q_exact on the full rng_next, as before.
+// K1's quad takes the table offset and the key from one multiply with 400 instead (pick_off400_key below, where
+// the argument is redone with its constants: band 2^32 - 1024 on the low word of 400 h').
 constexpr uint32_t PICK_HI_RARE_LO = 0xFFFFFF00u;  // low word of 100 h' at or above it: the exact path
+template <bool SHL64 = false>
 MSIM_HD uint32_t rng_next_hi(Rng &r)
 {
     const uint32_t h = (uint32_t)(rotl64(r.s0 + r.s1, 17) >> 32) + (uint32_t)(r.s0 >> 32);
-    (void)rng_next(r);  // the state update; its own output step is unused and compiles away
+    (void)rng_next<SHL64>(r);  // the state update; its own output step is unused and compiles away
     return h;
 }
 // p = floor(100 h / 2^32) and its key (the low word of 100 h): pick_q_fast_key on a high word.
 MSIM_HD uint32_t pick_p_key(uint32_t h, uint32_t &key) { return pick_q_fast_key((uint64_t)h << 32, key); }
+
+// What K1's quad runs instead: ONE 32 x 32 -> 64 multiply, 400 h' = t 2^32 + L (t < 400; v_mad_u64_u32), gives
+// both the table's byte offset and the key; pick_p_key above stays the checked definition it is compared with
+// (tests/native/k1pick400_check.cpp, over all 2^32 values of h').
+//   Offset: 400 h' / 2^32 = 4 * (100 h' / 2^32), and floor(floor(x) / 4) = floor(x / 4), so t >> 2 = p and
+//   t & ~3 = 4 p, the byte offset of info[p]: one v_and_b32 where the multiply with 100 needed a shift.
+//   Key: write t = 4 p + j (j = 0..3). Then 100 h' = p 2^32 + (j 2^32 + L) / 4 (the division is exact), i.e.
+//   pick_p_key's key is (j 2^32 + L) / 4. For L < PICK400_RARE_LO = 2^32 - 1024 that key is below
+//   (3 * 2^32 + 2^32 - 1024) / 4 = 2^32 - 256 = PICK_HI_RARE_LO for every j, and the carry argument above
+//   applies as it stands: q = p for h' and for h' + 1, with any low word. (Conversely pick_p_key's band,
+//   j = 3 and L >= 2^32 - 1024, lies inside L >= PICK400_RARE_LO: testing L alone flags a superset, 1024 / 2^32 =
+//   2.4e-7 of draws against 6e-8, next to the 3.3e-5 of the interval's check.)
+//   h' = 2^32 - 1, whose successor wraps: 400 h' = 399 * 2^32 + (2^32 - 400), L = 2^32 - 400 is in the band.
+constexpr uint32_t PICK400_RARE_LO = 0xFFFFFC00u;  // low word of 400 h' at or above it: the exact path
+MSIM_HD uint32_t pick_off400_key(uint32_t h, uint32_t &key)  // the byte offset of info[p]; key = low word of 400 h
+{
+    const uint64_t m = (uint64_t)h * 400u;
+    key = (uint32_t)m;
+    return (uint32_t)(m >> 32) & ~3u;
+}
 
 // ---------------------------------------------------------------- host table builders
 inline void build_log_table(LogTab *out)

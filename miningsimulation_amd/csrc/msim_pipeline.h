@@ -420,24 +420,26 @@ MSIM_HD uint32_t k1_draw_interval(Rng &ri, const double *__restrict__ invc, cons
     return (uint32_t)(ok ? q : (int32_t)interval_ms_of(u));
 #endif
 }
-// As draw_quad_fast, on the packed form and the high-word picker. The exponent limit of the folded table is
-// checked once per quad: the smallest high word of the four v's against K1P_VH_MIN.
+// As draw_quad_fast, on the packed form and the high-word picker by one multiply with 400 (msim_fastdraw.h
+// pick_off400_key), both streams stepped with the one-instruction s1 << 21 (msim_draws.h rng_next<true>). The
+// exponent limit of the folded table is checked once per quad: the smallest high word of the four v's against
+// K1P_VH_MIN.
 MSIM_HD bool k1p_quad_fast(Rng &ri, Rng &rp, const K1Pair *__restrict__ P, const PickTab *__restrict__ kp, FdConsts kc,
                            uint32_t (&I)[K1_QB], uint32_t (&info)[K1_QB])
 {
     uint32_t ki = 0, kk = 0, vmin = 0xFFFFFFFFu;
 #pragma unroll
     for (int q = 0; q < K1_QB; ++q) {
-        const uint64_t ui = rng_next(ri);
-        const uint32_t hp = rng_next_hi(rp);
+        const uint64_t ui = rng_next<true>(ri);
+        const uint32_t hp = rng_next_hi<true>(rp);
         uint32_t a, b, vh;
         I[q] = (uint32_t)k1p_interval_key(ui, P, a, vh, kc);
-        info[q] = kp->info[pick_p_key(hp, b)];
+        info[q] = *(const uint32_t *)((const char *)kp->info + pick_off400_key(hp, b));
         ki = a > ki ? a : ki;
         kk = b > kk ? b : kk;
         vmin = vh < vmin ? vh : vmin;
     }
-    return ki >= K1P_OK_HI || kk >= PICK_HI_RARE_LO || vmin < K1P_VH_MIN;
+    return ki >= K1P_OK_HI || kk >= PICK400_RARE_LO || vmin < K1P_VH_MIN;
 }
 // The redraw of a flagged quad: every interval by the general form first (3e-5 of draws only left the folded
 // table's exponent range), glibc's sequence for the one within the margin of a millisecond boundary; every pick
