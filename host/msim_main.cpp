@@ -28,6 +28,14 @@
 // correlation of the two sides and the ratio; in --json output a "contrast" object per miner (msim_contrast's
 // fields). P outside the points is a usage error.
 //
+// --classes (anywhere on the command line; composes with --errors, --json and --contrast): miners with equal
+// (perc, propagation, selfish) form a class (for a sweep: by its first point's miners, one map for all points), and
+// the exact on-device fold (msim_run_classes / msim_sweep_run_classes, one GPU) gives each class's found blocks,
+// share and stale rate per run as ONE column, with standard errors. After a network's miner lines one line per
+// class ("c5" gives three: the two pools and the 1 024 small miners); in --json output a "classes" array. With
+// --contrast P the contrast lines are per class. For the plain driver --json prints the report as one JSON line
+// and --runs R replaces SIM_RUNS.
+//
 // Build: make -C host
 // "c5" runs BASELINE configs[4] (2 pools + 1 024 small miners, integer weights summing to
 // W = 102 400, msim_config_create_weighted), which the reference's integer percentages cannot express.
@@ -124,13 +132,13 @@ static std::string Num(const char *fmt, double v, double scale = 1.0)
 }
 
 // The contrast lines of one point against point `baseline`, one per miner (contrasts.contrast_line in the package).
-static void PrintContrasts(size_t point, size_t baseline, const msim_contrast *c, size_t m)
+static void PrintContrasts(size_t point, size_t baseline, const msim_contrast *c, size_t m, const char *what = "Miner")
 {
     for (size_t k = 0; k < m; ++k) {
         const msim_contrast &x = c[k];
-        std::printf("  - Miner %zu of point %zu vs point %zu: found %s ± %s blocks (corr %s), ×%s ± %s;"
+        std::printf("  - %s %zu of point %zu vs point %zu: found %s ± %s blocks (corr %s), ×%s ± %s;"
                     " share %s ± %s of blocks (corr %s), ×%s ± %s; stale rate %s ± %s (corr %s)\n",
-                    k, point, baseline, Num("%+g", x.found_diff).c_str(), Num("%g", x.found_diff_se).c_str(),
+                    what, k, point, baseline, Num("%+g", x.found_diff).c_str(), Num("%g", x.found_diff_se).c_str(),
                     Num("%.3g", x.found_corr).c_str(), Num("%g", x.found_ratio).c_str(),
                     Num("%g", x.found_ratio_se).c_str(), Num("%+g%%", x.share_diff, 100.0).c_str(),
                     Num("%g%%", x.share_diff_se, 100.0).c_str(), Num("%.3g", x.share_corr).c_str(),
@@ -164,6 +172,48 @@ static void PrintReport(const std::vector<Miner> &miners, const std::vector<msim
     }
 }
 
+// Miner classes (--classes): miners with equal (perc, propagation, selfish), numbered by first appearance.
+struct Classes {
+    std::vector<uint32_t> class_of;
+    std::vector<uint32_t> members;   // per class
+    std::vector<uint64_t> weight;    // per class: the sum of its members' perc
+    uint32_t n() const { return (uint32_t)members.size(); }
+};
+
+static Classes GroupMiners(const std::vector<Miner> &miners)
+{
+    Classes c;
+    std::vector<size_t> first;  // a member of each class
+    for (size_t k = 0; k < miners.size(); ++k) {
+        size_t at = 0;
+        while (at < first.size() && !(miners[first[at]].perc == miners[k].perc &&
+                                      miners[first[at]].propagation == miners[k].propagation &&
+                                      miners[first[at]].is_selfish == miners[k].is_selfish))
+            ++at;
+        if (at == first.size()) {
+            first.push_back(k);
+            c.members.push_back(0);
+            c.weight.push_back(0);
+        }
+        c.class_of.push_back((uint32_t)at);
+        c.members[at] += 1;
+        c.weight[at] += miners[k].perc;
+    }
+    return c;
+}
+
+// One line per class (classes.class_line in the package).
+static void PrintClasses(const Classes &c, const msim_errors *e, uint64_t total_weight)
+{
+    for (uint32_t i = 0; i < c.n(); ++i)
+        std::printf("  - Class %u (%u miners, %g%% of network hashrate) found %g ± %s blocks i.e. %g%% ± %s of blocks."
+                    " Stale rate: %g%% ± %s.\n",
+                    i, c.members[i], (double)c.weight[i] * 100.0 / (double)total_weight, e[i].found_mean,
+                    PlusMinus(e[i].found_se, 1.0, "").c_str(), e[i].share_mean * 100,
+                    PlusMinus(e[i].share_se, 100.0, "%").c_str(), e[i].rate_mean * 100,
+                    PlusMinus(e[i].rate_se, 100.0, "%").c_str());
+}
+
 // One JSON line for a point: the network and its per-miner averages (the report's numbers).
 static void PrintJsonNumber(const char *sep, const char *name, double v)
 {
@@ -173,8 +223,37 @@ static void PrintJsonNumber(const char *sep, const char *name, double v)
         std::printf("%s\"%s\": %.17g", sep, name, v);
 }
 
+static void PrintJsonErrors(const msim_errors &e)
+{
+    PrintJsonNumber("\"errors\": {", "found_mean", e.found_mean);
+    PrintJsonNumber(", ", "found_se", e.found_se);
+    PrintJsonNumber(", ", "share_mean", e.share_mean);
+    PrintJsonNumber(", ", "share_se", e.share_se);
+    PrintJsonNumber(", ", "rate_mean", e.rate_mean);
+    PrintJsonNumber(", ", "rate_se", e.rate_se);
+    PrintJsonNumber(", ", "pooled_rate", e.pooled_rate);
+    PrintJsonNumber(", ", "pooled_rate_se", e.pooled_rate_se);
+    std::printf("}");
+}
+
+static void PrintJsonContrast(const msim_contrast &c)
+{
+    const double *v = &c.found_diff;
+    static const char *const names[16] = {
+        "found_diff", "found_diff_se", "found_corr", "found_ratio", "found_ratio_se", "stale_diff",
+        "stale_diff_se", "stale_corr", "share_diff", "share_diff_se", "share_corr", "share_ratio",
+        "share_ratio_se", "rate_diff", "rate_diff_se", "rate_corr"};
+    static_assert(sizeof(msim_contrast) == sizeof(double) * 16, "msim_contrast is 16 doubles");
+    for (int f = 0; f < 16; ++f) PrintJsonNumber(f ? ", " : ", \"contrast\": {", names[f], v[f]);
+    std::printf("}");
+}
+
+// With `classes` (--classes) a "classes" array follows the miners: per class its member count, hashrate, errors and,
+// with class_contrast, its contrast against the baseline point; `contrast` is then per miner as without classes.
 static void PrintJson(size_t point, const std::vector<Miner> &miners, const std::vector<msim_stats> &st, uint64_t runs,
-                      uint64_t total_weight, const msim_errors *errors = nullptr, const msim_contrast *contrast = nullptr)
+                      uint64_t total_weight, const msim_errors *errors = nullptr, const msim_contrast *contrast = nullptr,
+                      const Classes *classes = nullptr, const msim_errors *class_errors = nullptr,
+                      const msim_contrast *class_contrast = nullptr)
 {
     std::printf("{\"point\": %zu, \"runs\": %llu, \"total_weight\": %llu, \"miners\": [", point,
                 (unsigned long long)runs, (unsigned long long)total_weight);
@@ -186,30 +265,25 @@ static void PrintJson(size_t point, const std::vector<Miner> &miners, const std:
                     (double)st[i].blocks_found / (double)runs, st[i].blocks_share / (double)runs,
                     st[i].stale_rate / (double)runs);
         if (errors) {
-            const msim_errors &e = errors[i];
-            PrintJsonNumber(", \"errors\": {", "found_mean", e.found_mean);
-            PrintJsonNumber(", ", "found_se", e.found_se);
-            PrintJsonNumber(", ", "share_mean", e.share_mean);
-            PrintJsonNumber(", ", "share_se", e.share_se);
-            PrintJsonNumber(", ", "rate_mean", e.rate_mean);
-            PrintJsonNumber(", ", "rate_se", e.rate_se);
-            PrintJsonNumber(", ", "pooled_rate", e.pooled_rate);
-            PrintJsonNumber(", ", "pooled_rate_se", e.pooled_rate_se);
-            std::printf("}");
+            std::printf(", ");
+            PrintJsonErrors(errors[i]);
         }
-        if (contrast) {
-            const double *v = &contrast[i].found_diff;
-            static const char *const names[16] = {
-                "found_diff", "found_diff_se", "found_corr", "found_ratio", "found_ratio_se", "stale_diff",
-                "stale_diff_se", "stale_corr", "share_diff", "share_diff_se", "share_corr", "share_ratio",
-                "share_ratio_se", "rate_diff", "rate_diff_se", "rate_corr"};
-            static_assert(sizeof(msim_contrast) == sizeof(double) * 16, "msim_contrast is 16 doubles");
-            for (int f = 0; f < 16; ++f) PrintJsonNumber(f ? ", " : ", \"contrast\": {", names[f], v[f]);
-            std::printf("}");
-        }
+        if (contrast) PrintJsonContrast(contrast[i]);
         std::printf("}");
     }
-    std::printf("]}\n");
+    std::printf("]");
+    if (classes) {
+        std::printf(", \"classes\": [");
+        for (uint32_t c = 0; c < classes->n(); ++c) {
+            std::printf("%s{\"class\": %u, \"members\": %u, \"hashrate_perc\": %.17g, ", c ? ", " : "", c,
+                        classes->members[c], (double)classes->weight[c] * 100.0 / (double)total_weight);
+            PrintJsonErrors(class_errors[c]);
+            if (class_contrast) PrintJsonContrast(class_contrast[c]);
+            std::printf("}");
+        }
+        std::printf("]");
+    }
+    std::printf("}\n");
 }
 
 // RCCL prints a version banner on stdout when a communicator is created. The report on stdout must keep
@@ -255,6 +329,7 @@ struct SweepSpec {
     int gpus = 1;
     bool json = false;
     bool errors = false;
+    bool classes = false;  // --classes: statistics per class of identical miners (of the first point)
     long long contrast = -1;  // --contrast P: the baseline point, or -1
     bool shared_draws = false;  // --shared-draws: msim_sweep_create_ex(MSIM_SWEEP_SHARED_DRAWS)
 };
@@ -316,8 +391,38 @@ static int RunSweep(const SweepSpec &sp)
     const uint32_t m = cfgs.empty() ? 0 : msim_config_miner_count(cfgs[0]);
     std::vector<msim_stats> st(sp.points.size() * m);
     std::vector<msim_errors> errs;
-    std::vector<msim_contrast> con;  // [point != baseline, in order][miner]
-    if (rc == MSIM_OK && sp.contrast >= 0) {
+    std::vector<msim_contrast> con;  // [point != baseline, in order][miner], or [class] with --classes
+    Classes cls;
+    std::vector<msim_errors> cerrs;  // [point][class]
+    if (rc == MSIM_OK && sp.classes) {
+        cls = GroupMiners(sp.points[0]);
+        const uint32_t nc = cls.n();
+        std::vector<msim_pair> pairs;
+        for (uint32_t p = 0; p < sp.points.size() && sp.contrast >= 0; ++p)
+            for (uint32_t c = 0; c < nc && p != (uint32_t)sp.contrast; ++c) pairs.push_back({p, c, (uint32_t)sp.contrast, c});
+        std::vector<msim_moments> cmo(sp.points.size() * nc), mo(sp.errors ? st.size() : 0);
+        std::vector<msim_cross> cross(pairs.size());
+        rc = WithStdoutOnStderr([&] {
+            return msim_sweep_run_classes(sw, 0, sp.runs, sp.seed_base, 0, cls.class_of.data(), nc,
+                                          pairs.empty() ? nullptr : pairs.data(), (uint32_t)pairs.size(), st.data(),
+                                          nullptr, cmo.data(), nullptr, nullptr, pairs.empty() ? nullptr : cross.data());
+        });
+        if (rc == MSIM_OK && sp.errors)  // the miners' own standard errors need the miners' moments: a second pass
+            rc = WithStdoutOnStderr([&] {
+                return msim_sweep_run_moments(sw, 0, sp.runs, sp.seed_base, 0, st.data(), nullptr, mo.data(), nullptr, nullptr);
+            });
+        if (rc == MSIM_OK) {
+            cerrs.resize(cmo.size());
+            msim_moments_to_errors(cmo.data(), (uint32_t)cmo.size(), sp.runs, cerrs.data());
+            con.resize(pairs.size());
+            if (!pairs.empty())
+                msim_cross_to_contrasts(cmo.data(), nc, pairs.data(), cross.data(), (uint32_t)pairs.size(), sp.runs, con.data());
+            if (sp.errors) {
+                errs.resize(st.size());
+                msim_moments_to_errors(mo.data(), (uint32_t)mo.size(), sp.runs, errs.data());
+            }
+        }
+    } else if (rc == MSIM_OK && sp.contrast >= 0) {
         std::vector<msim_pair> pairs;
         for (uint32_t p = 0; p < sp.points.size(); ++p)
             for (uint32_t k = 0; k < m && p != (uint32_t)sp.contrast; ++k) pairs.push_back({p, k, (uint32_t)sp.contrast, k});
@@ -358,13 +463,20 @@ static int RunSweep(const SweepSpec &sp)
             const std::vector<msim_stats> ps(st.begin() + p * m, st.begin() + (p + 1) * m);
             const msim_errors *pe = sp.errors ? errs.data() + p * m : nullptr;
             const msim_contrast *pc = nullptr;
-            if (sp.contrast >= 0 && p != (size_t)sp.contrast) pc = con.data() + (p - (p > (size_t)sp.contrast)) * m;
+            const size_t cols = sp.classes ? cls.n() : m;  // columns of a point's contrasts
+            if (sp.contrast >= 0 && p != (size_t)sp.contrast && !con.empty())
+                pc = con.data() + (p - (p > (size_t)sp.contrast)) * cols;
+            const msim_errors *ce = sp.classes ? cerrs.data() + p * cls.n() : nullptr;
             if (sp.json) {
-                PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe, pc);
+                if (sp.classes)
+                    PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe, nullptr, &cls, ce, pc);
+                else
+                    PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe, pc);
             } else {
                 std::printf("Point %zu of %zu:\n", p + 1, sp.points.size());
                 PrintReport(sp.points[p], ps, sp.runs, sp.total_weight, days, pe);
-                if (pc) PrintContrasts(p, (size_t)sp.contrast, pc, m);
+                if (sp.classes) PrintClasses(cls, ce, sp.total_weight);
+                if (pc) PrintContrasts(p, (size_t)sp.contrast, pc, cols, sp.classes ? "Class" : "Miner");
             }
         }
     }
@@ -375,12 +487,15 @@ static int RunSweep(const SweepSpec &sp)
 
 int main(int argc, char **argv)
 {
-    bool errors = false;  // --errors, wherever it stands; the other arguments keep their positions
+    bool errors = false;   // --errors, wherever it stands; the other arguments keep their positions
+    bool classes = false;  // --classes, likewise
     {
         int kept = 1;
         for (int i = 1; i < argc; ++i) {
             if (std::string(argv[i]) == "--errors")
                 errors = true;
+            else if (std::string(argv[i]) == "--classes")
+                classes = true;
             else
                 argv[kept++] = argv[i];
         }
@@ -412,6 +527,7 @@ int main(int argc, char **argv)
                 else throw std::runtime_error("unknown option " + a);
             }
             sp.errors = errors;
+            sp.classes = classes;
             if (sp.contrast >= (long long)sp.points.size())
                 throw std::runtime_error("--contrast " + std::to_string(sp.contrast) + ": there are " +
                                          std::to_string(sp.points.size()) + " points");
@@ -421,6 +537,25 @@ int main(int argc, char **argv)
         }
         if (int rc = RunSweep(sp)) return die("sweep", rc);
         return 0;
+    }
+    // the plain driver: --json and --runs R wherever they stand, then the positional arguments
+    bool json = false;
+    uint64_t sim_runs = SIM_RUNS;
+    {
+        int kept = 1;
+        for (int i = 1; i < argc; ++i) {
+            if (std::string(argv[i]) == "--json")
+                json = true;
+            else if (std::string(argv[i]) == "--runs" && i + 1 < argc)
+                sim_runs = std::strtoull(argv[++i], nullptr, 10);
+            else
+                argv[kept++] = argv[i];
+        }
+        argc = kept;
+        if (sim_runs == 0) {
+            std::fprintf(stderr, "msim_main: --runs R: R is at least 1\n");
+            return 2;
+        }
     }
     const bool large = argc > 3 && std::string(argv[3]) == "c5";
     const auto miners{large ? SetupLargeNetwork() : SetupMiners()};
@@ -435,27 +570,48 @@ int main(int argc, char **argv)
         return die("config", rc);
 
     // main.cpp:201 (the reference names its thread count; here one stream drives each GPU)
-    std::printf("Running %d simulations in parallel using %d threads.\n", SIM_RUNS, n_gpus);
+    if (!json) std::printf("Running %llu simulations in parallel using %d threads.\n", (unsigned long long)sim_runs, n_gpus);
     std::vector<msim_stats> stats_total(miners.size());
-    std::vector<msim_errors> errs;
+    std::vector<msim_errors> errs, cerrs;
+    Classes cls;
+    if (classes) {
+        cls = GroupMiners(miners);
+        std::vector<msim_moments> cmo(cls.n());
+        cerrs.resize(cls.n());
+        if (int rc = WithStdoutOnStderr([&] {
+                return msim_run_classes(cfg, 0, sim_runs, seed_base, 0, cls.class_of.data(), cls.n(), nullptr, 0,
+                                        stats_total.data(), nullptr, cmo.data(), nullptr, nullptr, nullptr);
+            }))
+            return die("msim_run_classes", rc);
+        msim_moments_to_errors(cmo.data(), cls.n(), sim_runs, cerrs.data());
+    }
+    // with --classes and --errors the miners' own standard errors need the miners' moments: a second pass
     if (errors) {
         std::vector<msim_moments> mo(miners.size());
         errs.resize(miners.size());
         if (int rc = WithStdoutOnStderr([&] {
-                return msim_run_moments(cfg, 0, SIM_RUNS, seed_base, 0, stats_total.data(), nullptr, mo.data(), nullptr,
+                return msim_run_moments(cfg, 0, sim_runs, seed_base, 0, stats_total.data(), nullptr, mo.data(), nullptr,
                                         nullptr);
             }))
             return die("msim_run_moments", rc);
-        msim_moments_to_errors(mo.data(), (uint32_t)mo.size(), SIM_RUNS, errs.data());
-    } else if (int rc = WithStdoutOnStderr([&] {
-                   return msim_run_multi(cfg, 0, SIM_RUNS, seed_base, nullptr, (uint32_t)n_gpus, stats_total.data(),
-                                         nullptr);
-               }))
-        return die("msim_run_multi", rc);
+        msim_moments_to_errors(mo.data(), (uint32_t)mo.size(), sim_runs, errs.data());
+    } else if (!classes) {
+        if (int rc = WithStdoutOnStderr([&] {
+                return msim_run_multi(cfg, 0, sim_runs, seed_base, nullptr, (uint32_t)n_gpus, stats_total.data(), nullptr);
+            }))
+            return die("msim_run_multi", rc);
+    }
+    if (json) {
+        PrintJson(0, miners, stats_total, sim_runs, total_weight, errors ? errs.data() : nullptr, nullptr,
+                  classes ? &cls : nullptr, classes ? cerrs.data() : nullptr);
+        msim_config_destroy(cfg);
+        return 0;
+    }
     std::printf("\r100%% progress..\n");  // main.cpp:219-221
 
     const auto days{std::chrono::duration_cast<std::chrono::days>(SIM_DURATION)};
-    PrintReport(miners, stats_total, SIM_RUNS, total_weight, (long long)days.count(), errors ? errs.data() : nullptr);
+    PrintReport(miners, stats_total, sim_runs, total_weight, (long long)days.count(), errors ? errs.data() : nullptr);
+    if (classes) PrintClasses(cls, cerrs.data(), total_weight);
     msim_config_destroy(cfg);
     return 0;
 }

@@ -107,9 +107,9 @@ int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t du
  * kernel flags every run, so the retry kernel computes them all (what MSIM_SEL_FORCE_RETRY does on the entity
  * engine); at most 65 536 runs per launch then, the retry list's size.
  * A fourth, MSIM_MOMENTS_CHUNK_RUNS=<n> (n > 0), read only by msim_run_moments, msim_sweep_run_moments,
- * msim_run_contrasts and msim_sweep_run_contrasts at every call: a chunk of runs whose records stay in device
- * memory holds at most n runs (per point), so a few hundred runs exercise the chunk loop and its limb-by-limb
- * addition.
+ * msim_run_contrasts, msim_sweep_run_contrasts, msim_run_classes and msim_sweep_run_classes at every call: a chunk
+ * of runs whose records stay in device memory holds at most n runs (per point), so a few hundred runs exercise the
+ * chunk loop and its limb-by-limb addition.
  * Five more, MSIM_PIPE_TEST_*, read at every sizing and launch call of the honest pipeline (single networks and
  * shared-draw sweeps). Each only ever lowers a capacity below its 8-sigma size (the smaller of the natural value and
  * n, n > 0), and does so in the layout computation, so the buffers are exactly as large as the kernels are told:
@@ -460,6 +460,52 @@ typedef struct msim_contrast {
  * must pass msim_pairs_check for those counts. */
 void msim_cross_to_contrasts(const msim_moments *moments, uint32_t m, const msim_pair *pairs, const msim_cross *cross,
                              uint32_t n_pairs, uint64_t n_runs, msim_contrast *out);
+
+/* Miner classes: statistics of groups of miners ("the 1 024 small miners as one column", "everyone but the selfish
+ * miner", "what if miners 7 and 8 pooled"). (No reference counterpart: the reference prints three means per miner,
+ * main.cpp:224-234.) A class map is class_of[k] for k < m: a class index < n_classes, or MSIM_CLASS_NONE for a miner
+ * that belongs to no class. 1 <= n_classes <= m; empty classes are allowed, and so is a map that is all NONE. A
+ * sweep uses one map for all its points.
+ * The fold adds, per run, the records of a class's miners into one msim_run_record per class:
+ *   found = sum over class_of[k] == c of found_k,  stale = sum over class_of[k] == c of stale_k
+ * as uint32 sums, i.e. modulo 2^32. No record a launch writes can wrap them: a class's found blocks are at most the
+ * run's best height, and its stale blocks are fewer than the blocks drawn in the run. The folded records are laid
+ * out as a launch's with m = n_classes ([point][run][class]), and the best height stays the run's own, so
+ * msim_moments_launch and msim_cross_launch work on them unchanged. A class's terms are therefore share_t and rate_t
+ * of msim_moments applied to the CLASS record: the class as one miner, one rounded division of the class's counts.
+ * That is not the sum of its members' rounded terms (which differs from it by up to half a unit of 2^-32 per member
+ * for the share, and is a different quantity altogether for the stale rate: a sum of ratios, not the ratio of sums). */
+#define MSIM_CLASS_NONE 0xFFFFFFFFu
+/* Device-resident and asynchronous on `stream`, as msim_moments_launch: no allocation, no synchronisation,
+ * independent of any config, capturable. d_per_run: n_points * runs_per_point * m msim_run_record in msim_launch's /
+ * msim_sweep_launch's layout; d_class_of: m uint32_t in device memory; d_class_run: n_points * runs_per_point *
+ * n_classes msim_run_record, every one of them overwritten (nothing of the buffer is read or accumulated into, so it
+ * needs no clearing). An entry of the device map that is neither < n_classes nor MSIM_CLASS_NONE reads as NONE (the
+ * launch cannot see device memory; validate on the host with msim_classes_check). MSIM_E_INVALID, with nothing
+ * written, for m == 0, no points, more than 65 535 points, no runs, more than 2^32 - 1 runs per point,
+ * n_classes == 0, n_classes > m, or a null pointer. */
+int msim_fold_launch(uint32_t m, uint32_t n_points, uint64_t runs_per_point, const void *d_per_run,
+                     const void *d_class_of, uint32_t n_classes, void *d_class_run, void *stream);
+/* Host only: MSIM_OK when class_of is not null, 1 <= n_classes <= m and every entry is < n_classes or
+ * MSIM_CLASS_NONE, else MSIM_E_INVALID. */
+int msim_classes_check(uint32_t m, const uint32_t *class_of, uint32_t n_classes);
+/* msim_run_moments / msim_run_contrasts (and the sweep forms) per class: every chunk runs the launch, then
+ * msim_fold_launch into a chunk * n_points * n_classes record buffer, then msim_moments_launch (and msim_cross_launch
+ * when pairs are given) on the folded records with m = n_classes; chunks are added limb by limb and follow
+ * MSIM_MOMENTS_CHUNK_RUNS as those functions do. class_of: m entries, checked with msim_classes_check. out_stats (M,
+ * or n_points * M) and opt_sums stay per MINER, as msim_run's. out_class_moments: n_classes (n_points * n_classes)
+ * entries; opt_class_hist with opt_hist_spec: n_classes * 2 * (bins + 2) (times n_points) counts, or both NULL.
+ * pairs_or_NULL: n_pairs pairs of (point, CLASS) columns, checked with msim_pairs_check(n_classes, ...), with
+ * opt_cross: n_pairs entries; or NULL, 0 and NULL. */
+int msim_run_classes(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                     const uint32_t *class_of, uint32_t n_classes, const msim_pair *pairs_or_NULL, uint32_t n_pairs,
+                     msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_class_moments,
+                     const msim_hist_spec *opt_hist_spec, uint64_t *opt_class_hist, msim_cross *opt_cross);
+int msim_sweep_run_classes(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base,
+                           int device, const uint32_t *class_of, uint32_t n_classes, const msim_pair *pairs_or_NULL,
+                           uint32_t n_pairs, msim_stats *out_stats, msim_sums *opt_sums,
+                           msim_moments *out_class_moments, const msim_hist_spec *opt_hist_spec,
+                           uint64_t *opt_class_hist, msim_cross *opt_cross);
 
 /* Convert fixed-point sums to MinerStats-style doubles. */
 void msim_sums_to_stats(const msim_sums *sums, uint32_t n, msim_stats *out);

@@ -52,6 +52,12 @@ from .contrasts import (  # noqa: F401,E402
     split_cross,
 )
 
+from .classes import (  # noqa: F401,E402
+    classes_from_groups,
+    classes_of,
+    report_classes,
+)
+
 from . import model  # noqa: F401,E402  (first-order analytical stale-rate model, plot.py restated)
 
 __version__ = "0.1.0"

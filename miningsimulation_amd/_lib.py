@@ -71,7 +71,12 @@ EXPORTED = (
     "msim_run_contrasts",
     "msim_sweep_run_contrasts",
     "msim_cross_to_contrasts",
+    "msim_fold_launch",
+    "msim_classes_check",
+    "msim_run_classes",
+    "msim_sweep_run_classes",
 )
+MSIM_CLASS_NONE = 0xFFFFFFFF
 
 
 class MsimTiming(ctypes.Structure):
@@ -289,6 +294,17 @@ def _load() -> ctypes.CDLL:
     lib.msim_cross_to_contrasts.argtypes = [ctypes.POINTER(MsimMoments), u32, ctypes.POINTER(MsimPair),
                                             ctypes.POINTER(MsimCross), u32, u64, ctypes.POINTER(MsimContrast)]
     lib.msim_cross_to_contrasts.restype = None
+    lib.msim_fold_launch.argtypes = [u32, u32, u64, vp, vp, u32, vp, vp]
+    lib.msim_fold_launch.restype = ctypes.c_int
+    lib.msim_classes_check.argtypes = [u32, ctypes.POINTER(u32), u32]
+    lib.msim_classes_check.restype = ctypes.c_int
+    lib.msim_run_classes.argtypes = [vp, u64, u64, u32, ctypes.c_int, ctypes.POINTER(u32), u32,
+                                     ctypes.POINTER(MsimPair), u32, ctypes.POINTER(MsimStats),
+                                     ctypes.POINTER(MsimSums), ctypes.POINTER(MsimMoments),
+                                     ctypes.POINTER(MsimHistSpec), ctypes.POINTER(u64), ctypes.POINTER(MsimCross)]
+    lib.msim_run_classes.restype = ctypes.c_int
+    lib.msim_sweep_run_classes.argtypes = lib.msim_run_classes.argtypes
+    lib.msim_sweep_run_classes.restype = ctypes.c_int
     lib.msim_version.argtypes = []
     lib.msim_version.restype = ctypes.c_char_p
     return lib

@@ -1,7 +1,8 @@
 // msim_moments.hip — second moments and histograms of the per-run terms, reduced on the device from the records
 // and best heights a launch writes on request (include/msim.h: msim_moments_launch, msim_run_moments,
 // msim_sweep_run_moments, msim_moments_to_errors; the host conveniences at the end also serve msim_run_contrasts
-// and msim_sweep_run_contrasts, whose kernel is msim_cross.hip's). The arithmetic is msim_moments.h's.
+// and msim_sweep_run_contrasts, whose kernel is msim_cross.hip's, and msim_run_classes and msim_sweep_run_classes,
+// whose fold kernel is msim_fold.hip's). The arithmetic is msim_moments.h's.
 //
 // Kernel layout. Grid = (run chunks, miner tiles, points), 256 threads. A tile holds `tm` consecutive miners
 // (at most 256), and thread t owns miner t % tm of the tile on rows t / tm, t / tm + 256 / tm, ... of its run
@@ -178,17 +179,26 @@ struct CrossJob {
     uint32_t n_pairs;
     msim_cross *out;
 };
+// With `cls` (msim_run_classes), the map is checked and uploaded once, every chunk runs msim_fold_launch between the
+// launch and the reductions, and moments, histograms and cross sums are those of the folded records: mc = n_classes
+// columns per point where the plain forms have m. Sums and stats stay per miner.
+struct ClassJob {
+    const uint32_t *class_of;
+    uint32_t n_classes;
+};
 
 template <class WsBytes, class Launch>
 int run_moments_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, int device, msim_stats *out_stats,
                      msim_sums *opt_sums, msim_moments *out_moments, const msim_hist_spec *spec, uint64_t *opt_hist,
-                     bool general, WsBytes ws_bytes, Launch launch, const CrossJob *cross)
+                     bool general, WsBytes ws_bytes, Launch launch, const CrossJob *cross, const ClassJob *cls = nullptr)
 {
     if (!out_stats || !out_moments || runs == 0 || m == 0 || np == 0 || (spec != nullptr) != (opt_hist != nullptr))
         return MSIM_E_INVALID;
     if (spec && (spec->bins == 0 || spec->bins > msim::MOM_MAX_BINS || spec->share_shift > 63 || spec->rate_shift > 63))
         return MSIM_E_INVALID;
-    if (cross && (!cross->out || msim_pairs_check(m, np, cross->pairs, cross->n_pairs) != MSIM_OK)) return MSIM_E_INVALID;
+    if (cls && msim_classes_check(m, cls->class_of, cls->n_classes) != MSIM_OK) return MSIM_E_INVALID;
+    const uint32_t mc = cls ? cls->n_classes : m;  // columns of the moments, histograms and pairs
+    if (cross && (!cross->out || msim_pairs_check(mc, np, cross->pairs, cross->n_pairs) != MSIM_OK)) return MSIM_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
     uint64_t chunk = msim::MAX_LAUNCH_RUNS / np;
     const uint64_t by_bytes = MOM_CHUNK_BYTES / ((uint64_t)np * m * sizeof(msim_run_record));
@@ -199,33 +209,41 @@ int run_moments_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs,
     if (chunk == 0) return MSIM_E_INVALID;
     const size_t wsb = ws_bytes(chunk);
     if (!wsb) return MSIM_E_INVALID;
-    const size_t n_sums = 6 * (size_t)np * m, n_mom = msim::MOM_WORDS * (size_t)np * m;
-    const size_t n_hist = spec ? 2 * (size_t)(spec->bins + 2) * np * m : 0;
+    const size_t n_sums = 6 * (size_t)np * m, n_mom = msim::MOM_WORDS * (size_t)np * mc;
+    const size_t n_hist = spec ? 2 * (size_t)(spec->bins + 2) * np * mc : 0;
     const size_t n_cross = cross ? msim::CROSS_WORDS * (size_t)cross->n_pairs : 0;
     std::vector<uint64_t> acc_s(n_sums, 0), part_s(n_sums), acc_m(n_mom, 0), part_m(n_mom), acc_h(n_hist, 0),
         part_h(n_hist), acc_c(n_cross, 0), part_c(n_cross);
     uint32_t st[2] = {0, 0};
     // as msim_run: a workspace beyond the device's free memory is the network's size limit
     if (general && !msim::workspace_fits(wsb)) return MSIM_E_MINERS;
-    msim::DevBuf ws, sums, status, rec, bh, mom, hist, pairs, crs;
+    msim::DevBuf ws, sums, status, rec, bh, mom, hist, pairs, crs, map, crec;
     msim::DevStream stream;  // after the buffers: destroyed before they are freed
     if (!ws.alloc(wsb) || !sums.alloc(n_sums * sizeof(uint64_t)) || !status.alloc(sizeof(st)) ||
         !rec.alloc(chunk * np * m * sizeof(msim_run_record)) || !bh.alloc(chunk * np * sizeof(uint32_t)) ||
         !mom.alloc(n_mom * sizeof(uint64_t)) || (n_hist && !hist.alloc(n_hist * sizeof(uint64_t))) ||
         (cross && (!pairs.alloc(cross->n_pairs * sizeof(msim_pair)) || !crs.alloc(n_cross * sizeof(uint64_t)))) ||
+        (cls && (!map.alloc(m * sizeof(uint32_t)) || !crec.alloc(chunk * np * mc * sizeof(msim_run_record)))) ||
         !stream.create())
         return MSIM_E_HIP;
     hipStream_t s = stream.get();
     if (cross && hipMemcpy(pairs.get(), cross->pairs, cross->n_pairs * sizeof(msim_pair), hipMemcpyHostToDevice) != hipSuccess)
         return MSIM_E_HIP;
+    if (cls && hipMemcpy(map.get(), cls->class_of, m * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+        return MSIM_E_HIP;
+    const void *red = cls ? crec.get() : rec.get();  // the records the reductions read
     for (uint64_t off = 0; off < runs; off += chunk) {
         const uint64_t cn = runs - off < chunk ? runs - off : chunk;
         int rc = launch(run_begin + off, cn, sums.get(), rec.get(), bh.get(), status.get(), ws.get(), wsb, s);
         if (rc) return rc;
-        rc = msim_moments_launch(m, np, cn, rec.get(), bh.get(), spec, mom.get(), hist.get(), s);
+        if (cls) {
+            rc = msim_fold_launch(m, np, cn, rec.get(), map.get(), mc, crec.get(), s);
+            if (rc) return rc;
+        }
+        rc = msim_moments_launch(mc, np, cn, red, bh.get(), spec, mom.get(), hist.get(), s);
         if (rc) return rc;
         if (cross) {
-            rc = msim_cross_launch(m, np, cn, rec.get(), bh.get(), pairs.get(), cross->n_pairs, crs.get(), s);
+            rc = msim_cross_launch(mc, np, cn, red, bh.get(), pairs.get(), cross->n_pairs, crs.get(), s);
             if (rc) return rc;
         }
         if (hipMemcpyAsync(part_s.data(), sums.get(), n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -251,7 +269,7 @@ int run_moments_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs,
 
 int run_config(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
                msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments, const msim_hist_spec *spec,
-               uint64_t *opt_hist, const CrossJob *cross)
+               uint64_t *opt_hist, const CrossJob *cross, const ClassJob *cls = nullptr)
 {
     if (!cfg) return MSIM_E_INVALID;
     msim_pipeline_layout pl;
@@ -262,12 +280,12 @@ int run_config(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint
         [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
             return msim_launch(cfg, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
         },
-        cross);
+        cross, cls);
 }
 
 int run_sweep(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base, int device,
               msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_moments, const msim_hist_spec *spec,
-              uint64_t *opt_hist, const CrossJob *cross)
+              uint64_t *opt_hist, const CrossJob *cross, const ClassJob *cls = nullptr)
 {
     if (!sweep) return MSIM_E_INVALID;
     return run_moments_impl(
@@ -276,7 +294,7 @@ int run_sweep(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_poi
         [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
             return msim_sweep_launch(sweep, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
         },
-        cross);
+        cross, cls);
 }
 
 }  // namespace
@@ -316,6 +334,31 @@ int msim_sweep_run_contrasts(const msim_sweep *sweep, uint64_t run_begin, uint64
     const CrossJob job = {pairs, n_pairs, out_cross};
     return run_sweep(sweep, run_begin, runs_per_point, seed_base, device, out_stats, opt_sums, out_moments, nullptr,
                      nullptr, &job);
+}
+
+int msim_run_classes(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                     const uint32_t *class_of, uint32_t n_classes, const msim_pair *pairs_or_NULL, uint32_t n_pairs,
+                     msim_stats *out_stats, msim_sums *opt_sums, msim_moments *out_class_moments,
+                     const msim_hist_spec *opt_hist_spec, uint64_t *opt_class_hist, msim_cross *opt_cross)
+{
+    if ((pairs_or_NULL != nullptr) != (opt_cross != nullptr) || (!pairs_or_NULL && n_pairs)) return MSIM_E_INVALID;
+    const CrossJob job = {pairs_or_NULL, n_pairs, opt_cross};
+    const ClassJob cls = {class_of, n_classes};
+    return run_config(cfg, run_begin, n_runs, seed_base, device, out_stats, opt_sums, out_class_moments, opt_hist_spec,
+                      opt_class_hist, pairs_or_NULL ? &job : nullptr, &cls);
+}
+
+int msim_sweep_run_classes(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base,
+                           int device, const uint32_t *class_of, uint32_t n_classes, const msim_pair *pairs_or_NULL,
+                           uint32_t n_pairs, msim_stats *out_stats, msim_sums *opt_sums,
+                           msim_moments *out_class_moments, const msim_hist_spec *opt_hist_spec,
+                           uint64_t *opt_class_hist, msim_cross *opt_cross)
+{
+    if ((pairs_or_NULL != nullptr) != (opt_cross != nullptr) || (!pairs_or_NULL && n_pairs)) return MSIM_E_INVALID;
+    const CrossJob job = {pairs_or_NULL, n_pairs, opt_cross};
+    const ClassJob cls = {class_of, n_classes};
+    return run_sweep(sweep, run_begin, runs_per_point, seed_base, device, out_stats, opt_sums, out_class_moments,
+                     opt_hist_spec, opt_class_hist, pairs_or_NULL ? &job : nullptr, &cls);
 }
 
 }  // extern "C"

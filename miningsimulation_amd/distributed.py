@@ -143,10 +143,38 @@ def run_sharded_contrasts(sim, n_total: int, seed_base: int, pairs, run_begin: i
     return ContrastResult(points=[res], pairs=pairs, cross=cross, n_runs=n_total)
 
 
+def run_sharded_classes(sim, n_total: int, seed_base: int, class_of, n_classes: Optional[int] = None, pairs=None,
+                        hist=None, run_begin: int = 0, stream=None, launch: Optional[Callable] = None,
+                        launch_fold: Optional[Callable] = None, launch_moments: Optional[Callable] = None,
+                        launch_cross: Optional[Callable] = None, device=None, max_chunk: int = MAX_LAUNCH_RUNS):
+    """run_sharded_moments / run_sharded_contrasts per class of a class map (classes.classes_of,
+    classes_from_groups): every chunk runs msim_launch, msim_fold_launch into a device-resident [chunk, n_classes]
+    record buffer, then msim_moments_launch (and msim_cross_launch when `pairs` of (point 0, class) columns are
+    given) on the folded records, and everything travels in the ONE int64 buffer of the ONE all-reduce. Integer
+    sums over runs, so the result is bit-identical for every world size and partition.
+
+    Returns what Simulation.run_classes returns: a SimulationResult (stats_total and sums per miner, moments and
+    hist per class), inside a ContrastResult when pairs were given; identical on every rank. `launch_fold` replaces
+    sim.launch_fold as `launch_moments` replaces the moments launch (same signatures; the moments and cross
+    launches are given the folded records)."""
+    from .classes import class_count, class_map_struct
+    from .contrasts import Pair
+    from .simulation import ContrastResult
+
+    nc = class_count(class_of) if n_classes is None else int(n_classes)
+    class_map_struct(class_of, len(sim.miners), nc)  # ValueError for a map that does not fit
+    if pairs is not None:
+        pairs = [Pair(*q) for q in pairs]
+    res, cross = _run_sharded_moments(sim, n_total, seed_base, run_begin, stream, launch, launch_moments, device,
+                                      max_chunk, hist, pairs, launch_cross, ([int(c) for c in class_of], nc, launch_fold))
+    return res if pairs is None else ContrastResult(points=[res], pairs=pairs, cross=cross, n_runs=n_total)
+
+
 def _run_sharded_moments(sim, n_total, seed_base, run_begin, stream, launch, launch_moments, device, max_chunk, hist,
-                         pairs, launch_cross):
+                         pairs, launch_cross, classes=None):
     """(SimulationResult, cross sums or None): the body of run_sharded_moments, with the pairs' cross words behind
-    the histogram in the same buffer when `pairs` is given."""
+    the histogram in the same buffer when `pairs` is given. With `classes` = (class_of, n_classes, launch_fold or
+    None) every chunk is folded first, and moments, histogram and cross sums have mc = n_classes columns."""
     import contextlib
 
     import torch
@@ -155,30 +183,43 @@ def _run_sharded_moments(sim, n_total, seed_base, run_begin, stream, launch, lau
     from ._lib import MsimSums
     from .contrasts import CROSS_WORDS, cross_from_words, pairs_struct
     from .moments import MOMENT_WORDS, moments_from_words
-    from .simulation import SimulationResult, sums_to_stats
+    from .simulation import SimulationResult, _launch_cross, _launch_fold, _launch_moments, sums_to_stats
 
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     begin, n = shard(n_total, world, rank)
     m = len(sim.miners)
+    mc = classes[1] if classes is not None else m
     row = hist.bins + 2 if hist is not None else 0
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-    o_status, o_mom, o_hist = 6 * m, 6 * m + 2, 6 * m + 2 + MOMENT_WORDS * m
-    o_cross = o_hist + 2 * row * m
+    o_status, o_mom, o_hist = 6 * m, 6 * m + 2, 6 * m + 2 + MOMENT_WORDS * mc
+    o_cross = o_hist + 2 * row * mc
     n_pairs = len(pairs) if pairs is not None else 0
     buf = torch.zeros(o_cross + CROSS_WORDS * n_pairs, dtype=torch.int64, device=dev)
     if pairs is not None:
         import numpy as np
 
-        pairs_struct(pairs, 1, m)  # ValueError for a pair outside the network
+        pairs_struct(pairs, 1, mc)  # ValueError for a pair outside the network
         d_pairs = torch.from_numpy(np.asarray(pairs, dtype=np.uint32).reshape(-1, 4).view(np.int32)).to(dev)
         pcross = torch.zeros((n_pairs, CROSS_WORDS), dtype=torch.int64, device=dev)
     part = torch.zeros((m, 6), dtype=torch.int64, device=dev)
     pst = torch.zeros(2, dtype=torch.int32, device=dev)
-    pmom = torch.zeros((m, MOMENT_WORDS), dtype=torch.int64, device=dev)
-    phist = torch.zeros((m, 2, row), dtype=torch.int64, device=dev) if hist is not None else None
+    pmom = torch.zeros((mc, MOMENT_WORDS), dtype=torch.int64, device=dev)
+    phist = torch.zeros((mc, 2, row), dtype=torch.int64, device=dev) if hist is not None else None
     chunk = min(n, max_chunk)
     rec = torch.zeros((max(chunk, 1), m, 2), dtype=torch.int32, device=dev)
+    red = rec  # the records the reductions read
+    if classes is not None:
+        import numpy as np
+
+        d_map = torch.from_numpy(np.asarray(classes[0], dtype=np.uint32).view(np.int32)).to(dev)
+        red = torch.zeros((max(chunk, 1), mc, 2), dtype=torch.int32, device=dev)
+        fold = classes[2] or sim.launch_fold
+        # sim.launch_moments / launch_cross size their launches by the network; the folded records have mc columns
+        launch_moments = launch_moments or (lambda cn, r, b, o, hs, oh, stream=None: _launch_moments(
+            mc, 1, cn, r, b, o, hs, oh, stream))
+        launch_cross = launch_cross or (lambda cn, r, b, q, nq, o, stream=None: _launch_cross(
+            mc, 1, cn, r, b, q, nq, o, stream))
     bh = torch.zeros(max(chunk, 1), dtype=torch.int32, device=dev)
     ws = None
     if n and launch is None:
@@ -192,14 +233,16 @@ def _run_sharded_moments(sim, n_total, seed_base, run_begin, stream, launch, lau
             cn = min(chunk, n - off)
             (launch or sim.launch)(cn, run_begin + begin + off, seed_base, part, ws, pst, d_per_run=rec,
                                    d_best_height=bh, stream=stream)
-            (launch_moments or sim.launch_moments)(cn, rec, bh, pmom, hist, phist, stream=stream)
+            if classes is not None:
+                fold(cn, rec, d_map, mc, red, stream=stream)
+            (launch_moments or sim.launch_moments)(cn, red, bh, pmom, hist, phist, stream=stream)
             buf[:o_status] += part.view(-1)
             buf[o_status:o_mom] += pst
             buf[o_mom:o_hist] += pmom.view(-1)
             if hist is not None:
                 buf[o_hist:o_cross] += phist.view(-1)
             if pairs is not None:
-                (launch_cross or sim.launch_cross)(cn, rec, bh, d_pairs, n_pairs, pcross, stream=stream)
+                (launch_cross or sim.launch_cross)(cn, red, bh, d_pairs, n_pairs, pcross, stream=stream)
                 buf[o_cross:] += pcross.view(-1)
         if world > 1:
             dist.all_reduce(buf)
@@ -215,6 +258,6 @@ def _run_sharded_moments(sim, n_total, seed_base, run_begin, stream, launch, lau
         stats_total=sums_to_stats([[u64(x) for x in r] for r in rows]),
         sums=[MsimSums(r[0], r[1], u64(r[2]), u64(r[3]), u64(r[4]), u64(r[5])) for r in rows],
         n_runs=n_total,
-        moments=moments_from_words(host[o_mom:o_hist].view(m, MOMENT_WORDS).numpy()),
-        hist=host[o_hist:o_cross].view(m, 2, row).numpy().astype("uint64") if hist is not None else None,
+        moments=moments_from_words(host[o_mom:o_hist].view(mc, MOMENT_WORDS).numpy()),
+        hist=host[o_hist:o_cross].view(mc, 2, row).numpy().astype("uint64") if hist is not None else None,
     ), cross

@@ -22,6 +22,7 @@ import numpy as np
 from . import _lib
 from ._lib import (MSIM_SWEEP_SHARED_DRAWS, MsimCross, MsimMiner, MsimMoments, MsimRunRecord, MsimStats, MsimSums,
                    MsimSweepPlan, MsimTiming, check, lib)
+from .classes import class_count, class_map_struct
 from .contrasts import CROSS_WORDS, Pair, cross_from_words, pairs_struct
 from .moments import MOMENT_WORDS, HistSpec, moments_from_words
 
@@ -188,6 +189,55 @@ def _run_moments(fn, what: str, handle, n_points: int, m: int, n_runs: int, run_
     ) for p in range(n_points)]
 
 
+def _launch_fold(m: int, n_points: int, runs_per_point: int, d_per_run, d_class_of, n_classes: int, d_class_run,
+                 stream) -> None:
+    ptr = (lambda t: ctypes.c_void_p(t.data_ptr()))
+    sh = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    need = n_points * runs_per_point
+    if (d_per_run.numel() * d_per_run.element_size() < need * m * 8 or
+            d_class_of.numel() * d_class_of.element_size() < m * 4 or
+            d_class_run.numel() * d_class_run.element_size() < need * n_classes * 8):
+        raise ValueError("a buffer is smaller than the launch reads or writes")
+    check(lib.msim_fold_launch(m, n_points, runs_per_point, ptr(d_per_run), ptr(d_class_of), n_classes,
+                               ptr(d_class_run), sh), "msim_fold_launch")
+
+
+def _run_classes(fn, what: str, handle, n_points: int, m: int, n_runs: int, class_of: Sequence[int],
+                 n_classes: Optional[int], pairs: Optional[Sequence[Pair]], hist: Optional[HistSpec], run_begin: int,
+                 seed_base: int, device: int):
+    """The per-point SimulationResults of msim_run_classes / msim_sweep_run_classes (stats_total and sums per miner,
+    moments and hist per class), inside a ContrastResult when pairs of (point, class) columns were given."""
+    nc = class_count(class_of) if n_classes is None else int(n_classes)
+    cmap = class_map_struct(class_of, m, nc)
+    stats = (MsimStats * (n_points * m))()
+    sums = (MsimSums * (n_points * m))()
+    mom = (MsimMoments * (n_points * nc))()
+    row = hist.bins + 2 if hist is not None else 0
+    counts = (ctypes.c_uint64 * (n_points * nc * 2 * row))() if hist is not None else None
+    spec = ctypes.byref(hist.struct()) if hist is not None else None
+    if pairs is not None:
+        pairs = [Pair(*q) for q in pairs]
+        arr = pairs_struct(pairs, n_points, nc)
+        cross = (MsimCross * len(pairs))()
+    else:
+        arr, cross = None, None
+    check(fn(handle, run_begin, n_runs, seed_base & 0xFFFFFFFF, device, cmap, nc, arr, len(pairs) if pairs else 0,
+             stats, sums, mom, spec, counts, cross), what)
+    words = np.ctypeslib.as_array(ctypes.cast(mom, ctypes.POINTER(ctypes.c_uint64)), shape=(n_points * nc, MOMENT_WORDS))
+    h = np.ctypeslib.as_array(counts).reshape(n_points, nc, 2, row).copy() if hist is not None else None
+    points = [SimulationResult(
+        stats_total=[MinerStats(s.blocks_found, s.blocks_share, s.stale_rate) for s in stats[p * m:(p + 1) * m]],
+        sums=list(sums[p * m:(p + 1) * m]),
+        n_runs=n_runs,
+        moments=moments_from_words(words[p * nc:(p + 1) * nc]),
+        hist=h[p] if h is not None else None,
+    ) for p in range(n_points)]
+    if pairs is None:
+        return points
+    cw = np.ctypeslib.as_array(ctypes.cast(cross, ctypes.POINTER(ctypes.c_uint64)), shape=(len(pairs), CROSS_WORDS))
+    return ContrastResult(points=points, pairs=pairs, cross=cross_from_words(cw), n_runs=n_runs)
+
+
 def _miners_struct(miners: Sequence[Miner]):
     arr = (MsimMiner * len(miners))()
     for i, m in enumerate(miners):
@@ -279,6 +329,24 @@ class Simulation:
         """msim_cross_launch on the current device over a launch's records: d_pairs int32 [n_pairs, 4] and d_cross
         int64 [n_pairs, 12] (overwritten); the other buffers as launch_moments."""
         _launch_cross(len(self.miners), 1, n_runs, d_per_run, d_best_height, d_pairs, n_pairs, d_cross, stream)
+
+    def run_classes(self, n_runs: int, class_of: Sequence[int], pairs: Optional[Sequence[Pair]] = None,
+                    hist: Optional[HistSpec] = None, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
+                    device: int = 0, n_classes: Optional[int] = None):
+        """msim_run_classes: run_moments() per class of a class map (classes_of, classes_from_groups): `moments` and
+        `hist` have one entry per class (the class as one miner), stats_total and sums stay per miner. n_classes
+        defaults to one past the map's largest class. With `pairs` of (point, class) columns (every pair within
+        point 0, e.g. pairs_between_miners(n_classes)) the result is a ContrastResult whose `cross` is per class
+        too. error_bars, hist_quantile, contrasts and report_contrasts work on the results unchanged."""
+        res = _run_classes(lib.msim_run_classes, "msim_run_classes", self._h, 1, len(self.miners), n_runs, class_of,
+                           n_classes, pairs, hist, run_begin, seed_base, device)
+        return res if pairs is not None else res[0]
+
+    def launch_fold(self, n_runs: int, d_per_run, d_class_of, n_classes: int, d_class_run, stream=None) -> None:
+        """msim_fold_launch on the current device over a launch's records: d_per_run int32 [n_runs, M, 2], d_class_of
+        int32 [M] (NONE = -1) and d_class_run int32 [n_runs, n_classes, 2] (every record overwritten); launch_moments
+        and launch_cross of a Simulation of n_classes miners read d_class_run as they read d_per_run."""
+        _launch_fold(len(self.miners), 1, n_runs, d_per_run, d_class_of, n_classes, d_class_run, stream)
 
     def run_multi(self, n_runs: int, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
                   devices: Sequence[int] = (0,)) -> SimulationResult:
@@ -458,6 +526,20 @@ class Sweep:
         """msim_cross_launch over a sweep launch's records; d_pairs int32 [n_pairs, 4], d_cross int64 [n_pairs, 12]."""
         _launch_cross(self.m, len(self.sims), runs_per_point, d_per_run, d_best_height, d_pairs, n_pairs, d_cross,
                       stream)
+
+    def run_classes(self, runs_per_point: int, class_of: Sequence[int], pairs: Optional[Sequence[Pair]] = None,
+                    hist: Optional[HistSpec] = None, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
+                    device: int = 0, n_classes: Optional[int] = None):
+        """msim_sweep_run_classes: Simulation.run_classes over a sweep, one class map for all points. Per point a
+        SimulationResult with per-class `moments` and `hist`; with `pairs` of (point, class) columns (e.g.
+        pairs_vs_baseline(len(sweep), n_classes)) a ContrastResult over them."""
+        return _run_classes(lib.msim_sweep_run_classes, "msim_sweep_run_classes", self._h, len(self.sims), self.m,
+                            runs_per_point, class_of, n_classes, pairs, hist, run_begin, seed_base, device)
+
+    def launch_fold(self, runs_per_point: int, d_per_run, d_class_of, n_classes: int, d_class_run,
+                    stream=None) -> None:
+        """msim_fold_launch over a sweep launch's records; d_class_run int32 [n_points, runs_per_point, n_classes, 2]."""
+        _launch_fold(self.m, len(self.sims), runs_per_point, d_per_run, d_class_of, n_classes, d_class_run, stream)
 
     def workspace_bytes(self, runs_per_point: int) -> int:
         return int(lib.msim_sweep_workspace_bytes(self._h, runs_per_point))
