@@ -127,7 +127,22 @@ int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t du
  *   MSIM_WIDE_TEST_RCAP=<n>        candidate slots per run of a plain wide launch and of a shared-draw group's envelope
  *   MSIM_WIDE_TEST_POINT_RCAP=<n>  candidate slots per run of every point of a shared-draw group of more than one point
  * The large-network pipeline has no retry kernel: a run that outgrows a capacity fails (status[1] counts it, its
- * records stay unwritten, msim_run / msim_sweep_run return MSIM_E_CAPACITY). Unset, nothing changes. */
+ * records stay unwritten, msim_run / msim_sweep_run return MSIM_E_CAPACITY). Unset, nothing changes.
+ * Five more, MSIM_GEN_TEST_*, for the general engine (a network it serves alone, and the runs it finishes for the
+ * entity engine), read at every sizing and launch call. They too only ever lower (the smaller of the natural value
+ * and n) and act in the layout computation, before any offset; a value outside the stated range is ignored:
+ *   MSIM_GEN_TEST_LANES=<n> (n >= 1)     lanes of every tier, not rounded to waves: a lane then serves its runs in turn
+ *   MSIM_GEN_TEST_CAP1=<n> (n >= 8)      the window (blocks per chain) of tier 1,
+ *   MSIM_GEN_TEST_CAP2=<n> (n >= 8)      of tier 2,
+ *   MSIM_GEN_TEST_CAP3=<n> (n >= 8)      of tier 3. A lowered window removes no tier and adds none but the third below
+ *                                        a lowered second (short runs, whose last window is the second's 4 096
+ *                                        blocks), so a lowered last window can be too small: such a run fails
+ *                                        (status[1] counts it, its records stay unwritten, msim_run / msim_sweep_run
+ *                                        return MSIM_E_CAPACITY)
+ *   MSIM_GEN_TEST_LIST_CAP=<n> (n >= 1)  the length of the tier lists that the kernels are told; the lists keep their
+ *                                        natural allocation. A run that finds no room in a list fails in the same way
+ * msim_pipeline_info reports the lowered geometry (slice_runs: tier-1 lanes, segment_blocks: tier-1 window,
+ * blocks_per_run: last window). Unset, nothing changes. */
 int msim_config_is_wide(const msim_config *cfg);
 /* How many launches of this config the caller keeps in flight at once (default 1; e.g. 2 when steps
  * alternate over two HIP streams). The event-skipping pipeline plans its draw kernel's grid for it: three

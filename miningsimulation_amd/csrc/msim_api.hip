@@ -405,6 +405,27 @@ struct SelWs {
 constexpr double GEN_FALLBACK_BUDGET = 512.0 * (1 << 20);
 constexpr double GEN_BUDGET = 2048.0 * (1 << 20);
 
+// Test switches (MSIM_GEN_TEST_LANES, MSIM_GEN_TEST_CAP1 / CAP2 / CAP3, MSIM_GEN_TEST_LIST_CAP; msim.h): G's lanes,
+// windows and told list length lowered so that a few hundred short runs reach lane reuse, every tier, a last window
+// that is too small and full lists. Read at every sizing and launch call, as MSIM_MAX_SLICE_RUNS; a value below the
+// stated minimum is ignored. The limits go into the layout computation (msim_general_launch.h GenLimits): both
+// layouts below pass them, and every size, offset and kernel argument of G comes from those two.
+msim::GenLimits gen_test_limits()
+{
+    auto num = [](const char *name, long long least) {
+        const char *e = getenv(name);
+        const long long v = e ? atoll(e) : 0;
+        return v < least ? 0u : v >= 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)v;
+    };
+    msim::GenLimits lim;
+    lim.lanes = num("MSIM_GEN_TEST_LANES", 1);
+    lim.cap[0] = num("MSIM_GEN_TEST_CAP1", 8);
+    lim.cap[1] = num("MSIM_GEN_TEST_CAP2", 8);
+    lim.cap[2] = num("MSIM_GEN_TEST_CAP3", 8);
+    lim.list_cap = num("MSIM_GEN_TEST_LIST_CAP", 1);
+    return lim;
+}
+
 SelWs sel_ws_layout(uint32_t m, uint32_t np, uint64_t rpp, int64_t duration_ms, uint32_t max_nr = 1u << 22)
 {
     SelWs w;
@@ -426,7 +447,7 @@ SelWs sel_ws_layout(uint32_t m, uint32_t np, uint64_t rpp, int64_t duration_ms, 
     w.cold_lanes = e1 > w.err_cap ? e1 : (size_t)w.err_cap;
     w.cold_off = align256(w.list_off + (size_t)w.err_cap * 4);
     w.gen_off = align256(w.cold_off + w.cold_lanes * msim::SEL_NC * sizeof(msim::ColdAct));
-    w.g = msim::gen_ws_layout(m, duration_ms, w.err_cap, GEN_FALLBACK_BUDGET, true);
+    w.g = msim::gen_ws_layout(m, duration_ms, w.err_cap, GEN_FALLBACK_BUDGET, true, gen_test_limits());
     w.total = align256(w.gen_off + w.g.total);
     return w;
 }
@@ -701,7 +722,7 @@ struct GenOnlyWs {
 GenOnlyWs gen_only_layout(uint32_t m, uint32_t np, uint64_t rpp, int64_t duration_ms, bool selfish)
 {
     GenOnlyWs w;
-    w.g = msim::gen_ws_layout(m, duration_ms, (uint32_t)(rpp * np), GEN_BUDGET, selfish);
+    w.g = msim::gen_ws_layout(m, duration_ms, (uint32_t)(rpp * np), GEN_BUDGET, selfish, gen_test_limits());
     w.gen_off = 256;
     w.total = w.gen_off + w.g.total;
     return w;

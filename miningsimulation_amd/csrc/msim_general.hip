@@ -16,28 +16,6 @@
 
 namespace msim {
 
-struct GenDevStore {
-    uint32_t *o;          // this lane's owners [M][cap]
-    int64_t *a;           // this lane's arrivals [M][cap]
-    uint32_t *sz, *st, *pr;  // &array[lane]; miner k at [k * L]
-    size_t L;
-    uint32_t cap;
-    __device__ __forceinline__ uint32_t own(uint32_t k, uint32_t i) const { return o[(size_t)k * cap + i]; }
-    __device__ __forceinline__ int64_t arr(uint32_t k, uint32_t i) const { return a[(size_t)k * cap + i]; }
-    __device__ __forceinline__ void put(uint32_t k, uint32_t i, uint32_t ow, int64_t ar)
-    {
-        o[(size_t)k * cap + i] = ow;
-        a[(size_t)k * cap + i] = ar;
-    }
-    __device__ __forceinline__ void set_arr(uint32_t k, uint32_t i, int64_t ar) { a[(size_t)k * cap + i] = ar; }
-    __device__ __forceinline__ uint32_t size(uint32_t k) const { return sz[k * L]; }
-    __device__ __forceinline__ void set_size(uint32_t k, uint32_t n) { sz[k * L] = n; }
-    __device__ __forceinline__ void add_stale(uint32_t k) { st[k * L] += 1u; }
-    __device__ __forceinline__ uint32_t stale(uint32_t k) const { return st[k * L]; }
-    __device__ __forceinline__ void add_pre(uint32_t k, uint32_t v) { pr[k * L] += v; }
-    __device__ __forceinline__ uint32_t pre(uint32_t k) const { return pr[k * L]; }
-};
-
 __global__ __launch_bounds__(256) void msim_gen_kernel(const GenArgs a)
 {
     const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -66,9 +44,10 @@ __global__ __launch_bounds__(256) void msim_gen_kernel(const GenArgs a)
         GenOut o;
         if (!e.run(rng_seed(seed_interval(a.seed_base, run)), rng_seed(seed_picker(a.seed_base, run)), o)) {
             if ((o.err & GERR_CAP) && a.next) {
+                // an entry past the list's end is not stored; the next tier, which reads this count, counts
+                // those runs failed (above), once
                 const uint32_t pos = atomicAdd(a.next_count, 1u);
                 if (pos < a.list_cap) a.next[pos] = code;
-                else atomicAdd(a.counts + GEN_C_FAIL, 1u);
             } else {
                 atomicAdd(a.counts + GEN_C_FAIL, 1u);
             }

@@ -4,8 +4,13 @@
 // engine's retry kernel E2 could not finish) or from an index range (networks only G serves: selfish miners
 // in networks of more than 15 miners, more than 4 selfish miners); a run whose chains outgrow the window is
 // appended to the next tier's list. The last tier's window holds every block a run can have (gen_tiers).
+//
+// Everything but the launch functions is plain host / device arithmetic and compiles without HIP: the test-only
+// host program tests/native/gen_tiers_check.cpp walks the tiers over this layout and this store on the CPU.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 #include <math.h>
 #include <stddef.h>
 
@@ -72,16 +77,34 @@ inline uint32_t gen_last_cap(int64_t max_duration)
     top = (top + 255) / 256 * 256;
     return (uint32_t)(top > 4096 ? top : 4096);
 }
-inline int gen_tiers(uint32_t max_m, int64_t max_duration, double budget, GenTier (&t)[3], bool full)
+//
+// GenLimits: test switches (MSIM_GEN_TEST_*, include/msim.h; 0: none) that only LOWER a limit, so that a few hundred
+// short runs reach what the natural geometry reaches with year-long selfish majorities or not at all: a lane that
+// serves many runs, partial waves, every tier, a last window that is too small, full lists. They enter here,
+// before any offset is laid out, so every size and every kernel argument comes from the same lowered values.
+// Whether there is a last tier depends on `full` and its natural window, never on its lowered one, and each tier's
+// lanes come from its natural window: a lowered last window can then really be too small (MSIM_E_CAPACITY), and
+// lowering a window never raises a lane count.
+struct GenLimits {
+    uint32_t lanes = 0;              // lanes of every tier: min(natural, lanes), not rounded to waves
+    uint32_t cap[3] = {0u, 0u, 0u};  // window of tier 1 / 2 / 3: min(natural, cap[i])
+    uint32_t list_cap = 0;           // the list length the kernels are told: min(natural, list_cap); the lists keep
+                                     // their natural allocation (E2 appends to the first under its own bound)
+};
+inline int gen_tiers(uint32_t max_m, int64_t max_duration, double budget, GenTier (&t)[3], bool full,
+                     const GenLimits &lim = GenLimits())
 {
     const uint32_t caps[3] = {256u, 4096u, gen_last_cap(max_duration)};
-    const int nt = full && caps[2] > 4096u ? 3 : 2;
+    // the third tier exists when its natural window is larger than the second tier's: for runs too short to
+    // outgrow 4 096 blocks that is only so when a switch lowers the second window
+    const uint32_t cap2 = lim.cap[1] && lim.cap[1] < caps[1] ? lim.cap[1] : caps[1];
+    const int nt = full && caps[2] > cap2 ? 3 : 2;
     for (int i = 0; i < nt; ++i) {
         double l = floor(budget / gen_lane_bytes(max_m, caps[i]));
         l = l >= 64.0 ? floor(l / 64.0) * 64.0 : (l >= 1.0 ? l : 1.0);
         if (l > 65536.0) l = 65536.0;
-        t[i].cap = caps[i];
-        t[i].lanes = (size_t)l;
+        t[i].cap = lim.cap[i] && lim.cap[i] < caps[i] ? lim.cap[i] : caps[i];
+        t[i].lanes = lim.lanes && (double)lim.lanes < l ? (size_t)lim.lanes : (size_t)l;
     }
     return nt;
 }
@@ -95,16 +118,19 @@ inline bool gen_fits(uint32_t m, int64_t duration_ms, bool full)
 struct GenWs {
     GenTier tier[3];
     int nt;
-    uint32_t list_cap;
+    uint32_t list_cap;    // entries allocated per list (the stride of the three lists)
+    uint32_t list_limit;  // entries the kernels are told (<= list_cap; lower only under GenLimits::list_cap)
     size_t lists_off, sizes_off, owners_off, arrivals_off, total;
 };
 
-inline GenWs gen_ws_layout(uint32_t max_m, int64_t max_duration, uint32_t list_cap, double budget, bool full)
+inline GenWs gen_ws_layout(uint32_t max_m, int64_t max_duration, uint32_t list_cap, double budget, bool full,
+                           const GenLimits &lim = GenLimits())
 {
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     GenWs w;
-    w.nt = gen_tiers(max_m, max_duration, budget, w.tier, full);
+    w.nt = gen_tiers(max_m, max_duration, budget, w.tier, full, lim);
     w.list_cap = list_cap;
+    w.list_limit = lim.list_cap && lim.list_cap < list_cap ? lim.list_cap : list_cap;
     size_t lanes = 0, chain = 0;
     for (int i = 0; i < w.nt; ++i) {
         lanes = w.tier[i].lanes > lanes ? w.tier[i].lanes : lanes;
@@ -119,6 +145,31 @@ inline GenWs gen_ws_layout(uint32_t max_m, int64_t max_duration, uint32_t list_c
     return w;
 }
 
+// A lane's view of the workspace (msim_general.h "Store"): its chains [M][cap], contiguous per lane, and its
+// per-miner counters inside the [M][lanes] arrays (miner k at [k * L]). Pure index arithmetic.
+struct GenDevStore {
+    uint32_t *o;          // this lane's owners [M][cap]
+    int64_t *a;           // this lane's arrivals [M][cap]
+    uint32_t *sz, *st, *pr;  // &array[lane]; miner k at [k * L]
+    size_t L;
+    uint32_t cap;
+    MSIM_HD uint32_t own(uint32_t k, uint32_t i) const { return o[(size_t)k * cap + i]; }
+    MSIM_HD int64_t arr(uint32_t k, uint32_t i) const { return a[(size_t)k * cap + i]; }
+    MSIM_HD void put(uint32_t k, uint32_t i, uint32_t ow, int64_t ar)
+    {
+        o[(size_t)k * cap + i] = ow;
+        a[(size_t)k * cap + i] = ar;
+    }
+    MSIM_HD void set_arr(uint32_t k, uint32_t i, int64_t ar) { a[(size_t)k * cap + i] = ar; }
+    MSIM_HD uint32_t size(uint32_t k) const { return sz[k * L]; }
+    MSIM_HD void set_size(uint32_t k, uint32_t n) { sz[k * L] = n; }
+    MSIM_HD void add_stale(uint32_t k) { st[k * L] += 1u; }
+    MSIM_HD uint32_t stale(uint32_t k) const { return st[k * L]; }
+    MSIM_HD void add_pre(uint32_t k, uint32_t v) { pr[k * L] += v; }
+    MSIM_HD uint32_t pre(uint32_t k) const { return pr[k * L]; }
+};
+
+#if defined(__HIPCC__)
 hipError_t launch_gen(const GenArgs &a, hipStream_t s);
 hipError_t launch_gen_status(const uint32_t *counts, uint32_t *status, hipStream_t s);
 
@@ -130,7 +181,7 @@ inline hipError_t launch_gen_tiers(GenArgs a, const GenWs &w, char *gws, const u
     a.sizes = (uint32_t *)(gws + w.sizes_off);
     a.owners = (uint32_t *)(gws + w.owners_off);
     a.arrivals = (int64_t *)(gws + w.arrivals_off);
-    a.list_cap = w.list_cap;
+    a.list_cap = w.list_limit;
     for (int i = 0; i < w.nt; ++i) {
         a.cap = w.tier[i].cap;
         a.lanes = w.tier[i].lanes;
@@ -149,5 +200,6 @@ inline hipError_t launch_gen_tiers(GenArgs a, const GenWs &w, char *gws, const u
     }
     return hipSuccess;
 }
+#endif  // __HIPCC__
 
 }  // namespace msim

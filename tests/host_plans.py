@@ -15,6 +15,7 @@ import contextlib
 import ctypes
 import json
 import os
+import random
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,7 +29,8 @@ PIN = {"MSIM_K1_SLOTS": "8192"}
 SWITCHES = ("MSIM_K1_SLOTS", "MSIM_SELSEG", "MSIM_SEG_NSEG", "MSIM_MAX_SLICE_RUNS", "MSIM_PIPE_TEST_CAP",
             "MSIM_PIPE_TEST_LCAP", "MSIM_PIPE_TEST_POINT_CAP", "MSIM_PIPE_TEST_POINT_LCAP", "MSIM_PIPE_TEST_K2_KIND",
             "MSIM_WIDE_TEST_RCAP", "MSIM_WIDE_TEST_POINT_RCAP", "MSIM_FORCE_WIDE", "MSIM_FORCE_GENERAL",
-            "MSIM_NO_PIPELINE", "MSIM_SWEEP_SHARED_MAX_GROUP")
+            "MSIM_NO_PIPELINE", "MSIM_SWEEP_SHARED_MAX_GROUP", "MSIM_GEN_TEST_LANES", "MSIM_GEN_TEST_CAP1",
+            "MSIM_GEN_TEST_CAP2", "MSIM_GEN_TEST_CAP3", "MSIM_GEN_TEST_LIST_CAP")
 
 CONFIG_RUNS = (1, 257, 32_768, 1 << 22, 1 << 26)
 SWEEP_RUNS = (257, 8_192, 1 << 20)
@@ -61,7 +63,14 @@ def _net(msim, w, props, ids=None):
 def _configs(msim):
     """name -> (miners, duration, total weight, forced wide, kind)"""
     W5 = msim.C5_TOTAL_WEIGHT
+    rng = random.Random(11)  # the 5 000-miner and 100-miner networks of tests/test_gpu_general.py
+    big = [2000, 1500] + [rng.randint(1, 3) for _ in range(4998)]
+    rng = random.Random(5)
+    cuts = sorted(rng.sample(range(1, 700), 98))
+    hundred = [300] + [b - a for a, b in zip([0] + cuts, cuts + [700])]
     return {
+        "g_5000_honest": (_net(msim, big, [1000] * 5000), DAY, sum(big), False, "general"),
+        "g_100_one_selfish": ([msim.Miner(k, hundred[k], 1000, k == 0) for k in range(100)], 7 * DAY, 1000, False, "general"),
         "c1": (msim.PRESETS["c1"](), Y, 100, False, "honest"),
         "c2": (msim.PRESETS["c2"](), Y, 100, False, "honest"),
         "c3": (msim.PRESETS["c3"](), Y, 100, False, "selfish"),
@@ -135,6 +144,8 @@ def _sweeps(msim):
         "c5_with_a_general_point": [pt(net5, Y, W5), pt(c5(60_000), Y, W5)],
         # further engines and the split passes
         "selfish_grid_360": [pt(p) for p in msim.c4_grid()],
+        "six_selfish_c3_c2": [pt([msim.Miner(k, w, 1000, k < 5) for k, w in enumerate([10] * 7 + [15, 15])], 30 * DAY),
+                              pt(msim.PRESETS["c3"](), 30 * DAY), pt(msim.PRESETS["c2"](), 30 * DAY)],
         "a_shared_id_point": [pt(msim.setup_miners(1000)), pt(_net(msim, H, [1000] * 9, ids=[0, 0, 2, 3, 4, 5, 6, 7, 8]))],
         "honest_uniform_20": [pt(msim.setup_miners(d)) for d in delays20],
         "wide_uniform_20": [pt(_net(msim, wc, [d] * 17), 10**9, 101) for d in delays20],

@@ -192,3 +192,88 @@ def test_selfish_strategy_kats_on_general_engine(native_tests):
         oo, oa = (ctypes.c_uint32 * 4096)(), (ctypes.c_int64 * 4096)()
         m = lib.gen_kat(sm["id"], sm["propagation_ms"], code, t, bcs, own, arr, n, bown, barr, bn, oo, oa, 4096)
         assert [(oo[i], oa[i]) for i in range(m)] == chain(case["expect"]), case["name"]
+
+
+# ------------------------------------------------------------------ tiers, lane reuse and lists at lowered limits
+GEN_SWITCHES = ("MSIM_GEN_TEST_LANES", "MSIM_GEN_TEST_CAP1", "MSIM_GEN_TEST_CAP2", "MSIM_GEN_TEST_CAP3",
+                "MSIM_GEN_TEST_LIST_CAP")
+
+
+def _gen_tiers_check():
+    """build/gen_tiers_check, built here when missing or older than its sources (one builder at a time)."""
+    import fcntl
+    import os
+
+    import __graft_entry__ as ge
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = os.path.join(root, "build", "gen_tiers_check")
+    srcs = [os.path.join(root, "miningsimulation_amd", "csrc", h) for h in
+            ("msim_general.h", "msim_general_launch.h", "msim_model.h", "msim_draws.h")]
+    srcs.append(os.path.join(root, "tests", "native", "gen_tiers_check.cpp"))
+    os.makedirs(os.path.join(root, "build"), exist_ok=True)
+    with open(os.path.join(root, "build", ".gen_tiers_tests.lock"), "w") as lk:
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        if not os.path.exists(path) or os.path.getmtime(path) < max(os.path.getmtime(s) for s in srcs):
+            ge.build_gen_tiers_tests()
+    return path
+
+
+def test_tiers_at_lowered_limits_under_sanitizers():
+    """The tiers walked as the kernel walks them, over the layout of gen_ws_layout at 1, 3, 64 and 300 lanes and
+    windows of 8 / 16 / 64 and 16 / 64 / 256 blocks, every buffer a heap block of exactly its size filled with 0xFF,
+    under ASan + UBSan: every run equals the same run on a private zeroed store, and every run is finished or
+    counted failed exactly once (also with a list that holds half of what leaves tier 1)."""
+    import subprocess
+
+    r = subprocess.run([_gen_tiers_check()], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert r.stdout.strip().endswith("gen_tiers_check: ok")
+
+
+def test_gen_switches_out_of_range_or_high_change_no_plan(msim_lib_path, monkeypatch):
+    """Host side of the C ABI, no device: with the MSIM_GEN_TEST_* switches unset the plans are the recorded ones
+    (tests/test_host_plans.py: 5 000 honest miners, the 100-miner one-selfish network, configs[2], G sweeps); here, a
+    value above the natural one or outside its range changes nothing either, and a lower one shows and only lowers."""
+    import host_plans
+    import miningsimulation_amd as msim
+
+    def plans():
+        out = []
+        for s, n in sims:
+            out.append((s.workspace_bytes(n), s.pipeline_info(n)))
+        return out + [(sweep.workspace_bytes(32), sweep.plan(32))]
+
+    with host_plans._env():
+        cfg = host_plans._configs(msim)
+        sims = [(msim.Simulation(cfg[k][0], cfg[k][1], cfg[k][2]), n)
+                for k, n in (("g_5000_honest", 32), ("g_100_one_selfish", 64), ("c3", 512))]
+        sweep = msim.Sweep([list(p[0]) for p in host_plans._sweeps(msim)["six_selfish_c3_c2"]], 30 * DAY)
+        assert [i["uses_pipeline"] for _, i in plans()[:3]] == [4, 4, 3] and sweep.plan(32)["engine"] == 4
+        nat = plans()
+        for value in (str(2**31), "0", "-1", "junk"):
+            for k in GEN_SWITCHES:
+                monkeypatch.setenv(k, value)
+            assert plans() == nat, value
+        for k in GEN_SWITCHES[1:4]:
+            monkeypatch.setenv(k, "7")  # below the least window of 8 blocks
+        assert plans() == nat
+        for k in GEN_SWITCHES:
+            monkeypatch.delenv(k)
+        monkeypatch.setenv("MSIM_GEN_TEST_LIST_CAP", "1")  # tells the kernels less; the lists keep their allocation
+        assert plans() == nat
+        monkeypatch.delenv("MSIM_GEN_TEST_LIST_CAP")
+        monkeypatch.setenv("MSIM_GEN_TEST_LANES", "3")
+        monkeypatch.setenv("MSIM_GEN_TEST_CAP1", "16")
+        monkeypatch.setenv("MSIM_GEN_TEST_CAP2", "64")
+        monkeypatch.setenv("MSIM_GEN_TEST_CAP3", "1024")
+        low = plans()
+        for (wl, il), (wn, inn) in zip(low[:2], nat[:2]):
+            assert wl < wn
+            assert (il["slice_runs"], il["segment_blocks"]) == (3, 16) and inn["slice_runs"] >= 64
+            assert il["blocks_per_run"] < inn["blocks_per_run"]
+        assert low[0][1]["segments"] == 2 and low[0][1]["blocks_per_run"] == 64  # honest: two tiers
+        assert low[1][1]["segments"] == 3 and low[1][1]["blocks_per_run"] == 1024
+        assert low[2][0] < nat[2][0] and low[3][0] < nat[3][0]
+        for k in GEN_SWITCHES:
+            monkeypatch.delenv(k, raising=False)

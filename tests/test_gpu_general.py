@@ -34,7 +34,23 @@ def _rand_weights(m, rng, total=100):
     return [b[i + 1] - b[i] for i in range(m)]
 
 
-def _vs_oracle(msim, oracle, p, q, s, n, seed, dur, W=100, path=None, ids=None):
+def _status(sim, n, seed):
+    """A second launch of the same runs through msim_launch: its status words, and the five counter words at the head
+    of the workspace (msim_general_launch.h GEN_C_*: flagged, failed, tier lists 1..3)."""
+    import torch
+
+    m = len(sim.miners)
+    ws = torch.zeros(sim.workspace_bytes(n), dtype=torch.uint8, device="cuda")
+    sums = torch.zeros((m, 6), dtype=torch.int64, device="cuda")
+    st = torch.full((2,), -1, dtype=torch.int32, device="cuda")
+    sim.launch(n, 0, seed, sums, ws, st)
+    torch.cuda.synchronize()
+    return st.cpu().numpy().astype(np.int64), ws[:20].cpu().numpy().view(np.uint32).astype(np.int64), sums.cpu().numpy()
+
+
+def _vs_oracle(msim, oracle, p, q, s, n, seed, dur, W=100, path=None, ids=None, status=False):
+    """The result of msim_run; with status=True the pair (result, _status of a second launch), whose sums must be the
+    first launch's."""
     ids = list(range(len(p))) if ids is None else ids
     miners = [msim.Miner(ids[k], p[k], q[k], bool(s[k])) for k in range(len(p))]
     sim = msim.Simulation(miners, dur, total_weight=W)
@@ -51,6 +67,10 @@ def _vs_oracle(msim, oracle, p, q, s, n, seed, dur, W=100, path=None, ids=None):
         assert res.stats_total[k].blocks_found == int(f[:, k].sum())
         assert res.stats_total[k].blocks_share == sum(sh[:, k].tolist())
         assert res.stats_total[k].stale_rate == sum(rt[:, k].tolist())
+    if status:
+        st, counts, sums = _status(sim, n, seed)
+        assert sums.tobytes() == np.array([[getattr(x, f) for f, _ in x._fields_] for x in res.sums], dtype=np.int64).tobytes()
+        return res, (st, counts)
     return res
 
 
@@ -62,14 +82,26 @@ def test_gpu_general_100_miners_one_selfish(msim, oracle):
 
 
 def test_gpu_general_majority_two_selfish(msim, oracle):
-    """Two selfish miners holding 70 % (the entity engine flags these runs; E2 hands them to G)."""
-    _vs_oracle(msim, oracle, [35, 35, 20, 10], [1000] * 4, [True, True, False, False], 64, 4242, 30 * DAY, path=3)
+    """Two selfish miners holding 70 % (the entity engine flags these runs; E2 hands G those it cannot finish):
+    E1 flags at least one run, nothing fails, status[0] is what E1 flagged, G's first list holds no more than that,
+    and each tier's list no more than the one before."""
+    _, (st, counts) = _vs_oracle(msim, oracle, [35, 35, 20, 10], [1000] * 4, [True, True, False, False], 64, 4242,
+                                 30 * DAY, path=3, status=True)
+    print(f"two selfish miners, 64 runs: status {st.tolist()}, counters {counts.tolist()}")
+    assert st[1] == 0 and counts[1] == 0, (st, counts)
+    assert counts[0] > 0, (st, counts)
+    assert st[0] == counts[0] >= counts[2] >= counts[3] >= counts[4], (st, counts)
 
 
 def test_gpu_general_selfish_majority_one_miner(msim, oracle):
-    """One selfish miner with 60 % for a year: its lead grows all year, so the runs reach G's last window
-    (a run whose selfish miner never has to reveal ends with none of its blocks in the best chain)."""
-    _vs_oracle(msim, oracle, [60, 25, 15], [100, 100, 100], [True, False, False], 16, 99, D, path=3)
+    """One selfish miner with 60 % for a year: its lead grows all year (a run whose selfish miner never has to reveal
+    ends with none of its blocks in the best chain). The entity engine's settled form (msim_selm.h) serves a single
+    selfish miner whatever its lead, so E1 flags none of these runs and none reaches G: the status and the five
+    counter words of the launch are 0. G's last window is reached on the device through lowered windows
+    (tests/test_gpu_general_tiers.py)."""
+    _, (st, counts) = _vs_oracle(msim, oracle, [60, 25, 15], [100, 100, 100], [True, False, False], 16, 99, D, path=3,
+                                 status=True)
+    assert st.tolist() == [0, 0] and counts.tolist() == [0] * 5, (st, counts)
 
 
 def test_gpu_general_many_selfish(msim, oracle):

@@ -4,7 +4,10 @@ The file holds what the library answered, without a device, for single networks 
 sizes, slice sizes, segment geometry, engines, draw groups and every point's group, with and without the test switches
 that change a plan (tests/host_plans.py lists the cases and regenerates the file). It was recorded from the commit
 before the sweep planning, the launch-argument builders and the slice-fitting loop were each written once
-(5484533), so that rewrite, and any later one of the host code, has to reproduce every value. CPU only."""
+(5484533), so that rewrite, and any later one of the host code, has to reproduce every value. The general engine's
+networks (5 000 honest miners, 100 miners with one selfish, a sweep with a point only it serves) were added to the
+file from the commit before its test switches MSIM_GEN_TEST_* were written (f7767df): unset, they change no plan.
+CPU only."""
 import json
 
 import host_plans
