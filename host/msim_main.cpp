@@ -36,6 +36,13 @@
 // --contrast P the contrast lines are per class. For the plain driver --json prints the report as one JSON line
 // and --runs R replaces SIM_RUNS.
 //
+// --quantiles Q1,Q2,.. (anywhere on the command line; composes with every other option): the exact quantiles of every
+// miner's per-run found blocks, share and stale rate, selected on the device (msim_run_order_stats /
+// msim_sweep_run_order_stats, one GPU, one more pass over the runs): the k-th smallest of the runs' values with
+// k = max(1, ceil(q runs)). After a network's other lines one line per miner (per class with --classes, per point
+// for a sweep); in --json output a "quantiles" object with the ranks and, per column and quantity (found, stale,
+// share, rate; the last two in units of 2^-32), [value, below, equal] per rank.
+//
 // Build: make -C host
 // "c5" runs BASELINE configs[4] (2 pools + 1 024 small miners, integer weights summing to
 // W = 102 400, msim_config_create_weighted), which the reference's integer percentages cannot express.
@@ -214,6 +221,107 @@ static void PrintClasses(const Classes &c, const msim_errors *e, uint64_t total_
                     PlusMinus(e[i].rate_se, 100.0, "%").c_str());
 }
 
+// --quantiles: the requested quantiles, their 0-based ranks among `runs` values, and msim_order_stat
+// [point][column][4][rank] once selected (columns: miners, or classes with --classes).
+struct Quantiles {
+    std::vector<double> q;
+    std::vector<uint64_t> ranks;
+    std::vector<msim_order_stat> order;
+    uint32_t cols = 0;
+    bool on() const { return !q.empty(); }
+    void SetRuns(uint64_t runs)
+    {
+        ranks.clear();
+        for (double x : q) {
+            const double k = std::ceil(x * (double)runs);  // hist_quantile's k
+            ranks.push_back(k < 1.0 ? 0 : (uint64_t)k - 1);
+        }
+    }
+    const msim_order_stat *at(size_t point, size_t col, size_t quantity) const
+    {
+        return order.data() + ((point * cols + col) * 4 + quantity) * ranks.size();
+    }
+};
+
+static Quantiles ParseQuantiles(const std::string &s)
+{
+    Quantiles qs;
+    std::stringstream ss(s);
+    std::string tok;
+    while (std::getline(ss, tok, ',')) {
+        size_t used = 0;
+        const double x = std::stod(tok, &used);
+        if (used != tok.size() || !(x >= 0.0 && x <= 1.0)) throw std::runtime_error("--quantiles Q1,Q2,..: each within [0, 1]");
+        qs.q.push_back(x);
+    }
+    if (qs.q.empty() || qs.q.size() > MSIM_MAX_RANKS)
+        throw std::runtime_error("--quantiles Q1,Q2,..: 1 to " + std::to_string(MSIM_MAX_RANKS) + " quantiles");
+    return qs;
+}
+
+// What follows a line's head (quantiles.quantile_columns in the package).
+static void PrintQuantileColumns(const Quantiles &qs, size_t point, size_t col)
+{
+    static const char *const what[3] = {" blocks found: ", "; share of blocks: ", "; stale rate: "};
+    static const size_t quantity[3] = {0, 2, 3};
+    for (int w = 0; w < 3; ++w) {
+        std::printf("%s", what[w]);
+        const msim_order_stat *o = qs.at(point, col, quantity[w]);
+        for (size_t j = 0; j < qs.q.size(); ++j) {
+            std::printf("%sq%g = ", j ? ", " : "", qs.q[j]);
+            if (w == 0)
+                std::printf("%llu", (unsigned long long)o[j].value);
+            else
+                std::printf("%g%%", (double)o[j].value * 0x1.0p-32 * 100);
+        }
+    }
+    std::printf(".\n");
+}
+
+// One line per miner, or per class (quantiles.report_quantiles in the package).
+static void PrintQuantiles(const Quantiles &qs, size_t point, const std::vector<Miner> &miners, const Classes *classes,
+                           uint64_t total_weight)
+{
+    for (size_t c = 0; c < qs.cols; ++c) {
+        if (classes)
+            std::printf("  - Class %zu (%u miners, %g%% of network hashrate)", c, classes->members[c],
+                        (double)classes->weight[c] * 100.0 / (double)total_weight);
+        else
+            std::printf("  - Miner %u (%llu%% of network hashrate)", miners[c].id, (unsigned long long)miners[c].perc);
+        PrintQuantileColumns(qs, point, c);
+    }
+}
+
+static std::string JsonQuantiles(const Quantiles &qs, size_t point, bool classes)
+{
+    std::string s = ", \"quantiles\": {\"columns\": \"";
+    s += classes ? "classes" : "miners";
+    s += "\", \"q\": [";
+    char buf[96];
+    for (size_t j = 0; j < qs.q.size(); ++j) {
+        std::snprintf(buf, sizeof(buf), "%s%.17g", j ? ", " : "", qs.q[j]);
+        s += buf;
+    }
+    s += "], \"ranks\": [";
+    for (size_t j = 0; j < qs.ranks.size(); ++j) s += (j ? ", " : "") + std::to_string(qs.ranks[j]);
+    s += "], \"order\": [";
+    for (size_t c = 0; c < qs.cols; ++c) {
+        s += c ? ", [" : "[";
+        for (size_t q = 0; q < 4; ++q) {
+            s += q ? ", [" : "[";
+            const msim_order_stat *o = qs.at(point, c, q);
+            for (size_t j = 0; j < qs.ranks.size(); ++j) {
+                std::snprintf(buf, sizeof(buf), "%s[%llu, %llu, %llu]", j ? ", " : "", (unsigned long long)o[j].value,
+                              (unsigned long long)o[j].below, (unsigned long long)o[j].equal);
+                s += buf;
+            }
+            s += "]";
+        }
+        s += "]";
+    }
+    return s + "]}";
+}
+
 // One JSON line for a point: the network and its per-miner averages (the report's numbers).
 static void PrintJsonNumber(const char *sep, const char *name, double v)
 {
@@ -253,7 +361,7 @@ static void PrintJsonContrast(const msim_contrast &c)
 static void PrintJson(size_t point, const std::vector<Miner> &miners, const std::vector<msim_stats> &st, uint64_t runs,
                       uint64_t total_weight, const msim_errors *errors = nullptr, const msim_contrast *contrast = nullptr,
                       const Classes *classes = nullptr, const msim_errors *class_errors = nullptr,
-                      const msim_contrast *class_contrast = nullptr)
+                      const msim_contrast *class_contrast = nullptr, const std::string &tail = std::string())
 {
     std::printf("{\"point\": %zu, \"runs\": %llu, \"total_weight\": %llu, \"miners\": [", point,
                 (unsigned long long)runs, (unsigned long long)total_weight);
@@ -283,7 +391,7 @@ static void PrintJson(size_t point, const std::vector<Miner> &miners, const std:
         }
         std::printf("]");
     }
-    std::printf("}\n");
+    std::printf("%s}\n", tail.c_str());  // --quantiles: its object
 }
 
 // RCCL prints a version banner on stdout when a communicator is created. The report on stdout must keep
@@ -330,6 +438,7 @@ struct SweepSpec {
     bool json = false;
     bool errors = false;
     bool classes = false;  // --classes: statistics per class of identical miners (of the first point)
+    Quantiles quantiles;   // --quantiles Q1,Q2,..
     long long contrast = -1;  // --contrast P: the baseline point, or -1
     bool shared_draws = false;  // --shared-draws: msim_sweep_create_ex(MSIM_SWEEP_SHARED_DRAWS)
 };
@@ -457,6 +566,19 @@ static int RunSweep(const SweepSpec &sp)
             return msim_sweep_run_multi(sw, 0, sp.runs, sp.seed_base, nullptr, (uint32_t)sp.gpus, st.data(), nullptr);
         });
     }
+    Quantiles qs = sp.quantiles;
+    if (rc == MSIM_OK && qs.on()) {  // one more pass over the runs: every point's records stay on the device
+        if (sp.classes && cls.class_of.empty()) cls = GroupMiners(sp.points[0]);
+        qs.SetRuns(sp.runs);
+        qs.cols = sp.classes ? cls.n() : m;
+        qs.order.resize(sp.points.size() * qs.cols * 4 * qs.ranks.size());
+        std::vector<msim_stats> again(st.size());
+        rc = WithStdoutOnStderr([&] {
+            return msim_sweep_run_order_stats(sw, 0, sp.runs, sp.seed_base, 0, sp.classes ? cls.class_of.data() : nullptr,
+                                              sp.classes ? cls.n() : 0, qs.ranks.data(), (uint32_t)qs.ranks.size(),
+                                              again.data(), nullptr, qs.order.data());
+        });
+    }
     if (rc == MSIM_OK) {
         const long long days = sp.duration_ms / 86'400'000;
         for (size_t p = 0; p < sp.points.size(); ++p) {
@@ -468,15 +590,17 @@ static int RunSweep(const SweepSpec &sp)
                 pc = con.data() + (p - (p > (size_t)sp.contrast)) * cols;
             const msim_errors *ce = sp.classes ? cerrs.data() + p * cls.n() : nullptr;
             if (sp.json) {
+                const std::string tail = qs.on() ? JsonQuantiles(qs, p, sp.classes) : std::string();
                 if (sp.classes)
-                    PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe, nullptr, &cls, ce, pc);
+                    PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe, nullptr, &cls, ce, pc, tail);
                 else
-                    PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe, pc);
+                    PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe, pc, nullptr, nullptr, nullptr, tail);
             } else {
                 std::printf("Point %zu of %zu:\n", p + 1, sp.points.size());
                 PrintReport(sp.points[p], ps, sp.runs, sp.total_weight, days, pe);
                 if (sp.classes) PrintClasses(cls, ce, sp.total_weight);
                 if (pc) PrintContrasts(p, (size_t)sp.contrast, pc, cols, sp.classes ? "Class" : "Miner");
+                if (qs.on()) PrintQuantiles(qs, p, sp.points[p], sp.classes ? &cls : nullptr, sp.total_weight);
             }
         }
     }
@@ -489,10 +613,18 @@ int main(int argc, char **argv)
 {
     bool errors = false;   // --errors, wherever it stands; the other arguments keep their positions
     bool classes = false;  // --classes, likewise
+    Quantiles quantiles;   // --quantiles Q1,Q2,.., likewise
     {
         int kept = 1;
         for (int i = 1; i < argc; ++i) {
-            if (std::string(argv[i]) == "--errors")
+            if (std::string(argv[i]) == "--quantiles" && i + 1 < argc) {
+                try {
+                    quantiles = ParseQuantiles(argv[++i]);
+                } catch (const std::exception &e) {
+                    std::fprintf(stderr, "msim_main: %s\n", e.what());
+                    return 2;
+                }
+            } else if (std::string(argv[i]) == "--errors")
                 errors = true;
             else if (std::string(argv[i]) == "--classes")
                 classes = true;
@@ -528,6 +660,7 @@ int main(int argc, char **argv)
             }
             sp.errors = errors;
             sp.classes = classes;
+            sp.quantiles = quantiles;
             if (sp.contrast >= (long long)sp.points.size())
                 throw std::runtime_error("--contrast " + std::to_string(sp.contrast) + ": there are " +
                                          std::to_string(sp.points.size()) + " points");
@@ -601,9 +734,22 @@ int main(int argc, char **argv)
             }))
             return die("msim_run_multi", rc);
     }
+    if (quantiles.on()) {  // one more pass over the runs: their records stay on the device
+        quantiles.SetRuns(sim_runs);
+        quantiles.cols = classes ? cls.n() : (uint32_t)miners.size();
+        quantiles.order.resize((size_t)quantiles.cols * 4 * quantiles.ranks.size());
+        std::vector<msim_stats> again(miners.size());
+        if (int rc = WithStdoutOnStderr([&] {
+                return msim_run_order_stats(cfg, 0, sim_runs, seed_base, 0, classes ? cls.class_of.data() : nullptr,
+                                            classes ? cls.n() : 0, quantiles.ranks.data(), (uint32_t)quantiles.ranks.size(),
+                                            again.data(), nullptr, quantiles.order.data());
+            }))
+            return die("msim_run_order_stats", rc);
+    }
     if (json) {
         PrintJson(0, miners, stats_total, sim_runs, total_weight, errors ? errs.data() : nullptr, nullptr,
-                  classes ? &cls : nullptr, classes ? cerrs.data() : nullptr);
+                  classes ? &cls : nullptr, classes ? cerrs.data() : nullptr, nullptr,
+                  quantiles.on() ? JsonQuantiles(quantiles, 0, classes) : std::string());
         msim_config_destroy(cfg);
         return 0;
     }
@@ -612,6 +758,7 @@ int main(int argc, char **argv)
     const auto days{std::chrono::duration_cast<std::chrono::days>(SIM_DURATION)};
     PrintReport(miners, stats_total, sim_runs, total_weight, (long long)days.count(), errors ? errs.data() : nullptr);
     if (classes) PrintClasses(cls, cerrs.data(), total_weight);
+    if (quantiles.on()) PrintQuantiles(quantiles, 0, miners, classes ? &cls : nullptr, total_weight);
     msim_config_destroy(cfg);
     return 0;
 }

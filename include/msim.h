@@ -109,7 +109,9 @@ int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t du
  * A fourth, MSIM_MOMENTS_CHUNK_RUNS=<n> (n > 0), read only by msim_run_moments, msim_sweep_run_moments,
  * msim_run_contrasts, msim_sweep_run_contrasts, msim_run_classes and msim_sweep_run_classes at every call: a chunk
  * of runs whose records stay in device memory holds at most n runs (per point), so a few hundred runs exercise the
- * chunk loop and its limb-by-limb addition.
+ * chunk loop and its limb-by-limb addition. msim_run_order_stats and msim_sweep_run_order_stats follow it too.
+ * MSIM_RANK_TEST_WG_RUNS=<n> (n > 0), read at every msim_rank_count_launch: a workgroup of the count kernel takes at
+ * most n runs, so a few hundred runs give several workgroups along the run axis (see msim_rank_count_launch).
  * Five more, MSIM_PIPE_TEST_*, read at every sizing and launch call of the honest pipeline (single networks and
  * shared-draw sweeps). Each only ever lowers a capacity below its 8-sigma size (the smaller of the natural value and
  * n, n > 0), and does so in the layout computation, so the buffers are exactly as large as the kernels are told:
@@ -521,6 +523,89 @@ int msim_sweep_run_classes(const msim_sweep *sweep, uint64_t run_begin, uint64_t
                            uint32_t n_pairs, msim_stats *out_stats, msim_sums *opt_sums,
                            msim_moments *out_class_moments, const msim_hist_spec *opt_hist_spec,
                            uint64_t *opt_class_hist, msim_cross *opt_cross);
+
+/* Exact quantiles: order statistics of the per-run terms, selected on the device from the records a launch writes
+ * on request. (No reference counterpart: the reference prints three means per miner, main.cpp:224-234.) For one run
+ * and one column (a miner, or a class after msim_fold_launch) the four quantities are found, stale, share_t and
+ * rate_t exactly as defined for msim_moments, each a uint64 key (found and stale zero-extended); quantity index
+ * 0 = found, 1 = stale, 2 = share_t, 3 = rate_t. For a 0-based rank r < N over the N runs of a column:
+ *   value = the r-th smallest key,  below = #{key < value},  equal = #{key == value}  (below <= r < below + equal).
+ * The k-th smallest of a multiset of integers does not depend on how the runs are split into workgroups, chunks,
+ * launches or ranks, and the selection works from digit counts that are plain integer sums, so they can be
+ * all-reduced. The q-quantile in msim_moments' histogram convention is the k-th smallest with k = max(1, ceil(q N)),
+ * i.e. rank k - 1.
+ * The method is MSD radix selection: MSIM_RANK_PASSES passes of 8 bits from the top of the key. A pass is one count
+ * launch per record buffer, which ADDS to the 256 digit counts of every (point, column, quantity, rank) row the keys
+ * that carry the row's prefix, then one step launch, which picks per row the digit whose running total first
+ * exceeds what remains of the rank, narrows the row's {prefix, remaining} state and clears the counts. Count and
+ * step are separate launches on one stream; the kernel boundary is their only synchronisation. */
+#define MSIM_MAX_RANKS 32u
+#define MSIM_RANK_PASSES 8u
+typedef struct msim_order_stat {
+    uint64_t value, below, equal;
+} msim_order_stat; /* per [point][column][4][rank] */
+
+/* Host only: the bytes of workspace the launches below need for m columns, n_points points and n_ranks ranks
+ * (state of every row plus n_points * m * 4 * n_ranks * 256 uint64 counts); 0 for m == 0, no points, more than
+ * 65 535 points or n_ranks outside 1..MSIM_MAX_RANKS. */
+size_t msim_rank_workspace_bytes(uint32_t m, uint32_t n_points, uint32_t n_ranks);
+/* Host only: where the counts lie inside the workspace, as a byte offset and a number of uint64 words, for an
+ * all-reduce (sum) between the count launches and the step launch of a pass when the runs are spread over ranks of
+ * a process group. Every rank must have begun with the same m, n_points and ranks. MSIM_E_INVALID as above or for a
+ * null pointer. */
+int msim_rank_counts_view(uint32_t m, uint32_t n_points, uint32_t n_ranks, size_t *offset, size_t *words);
+/* The launches: device-resident and asynchronous on `stream`, as msim_moments_launch: no allocation, no
+ * synchronisation, independent of any config. d_ws: ws_bytes >= msim_rank_workspace_bytes(...) of device memory,
+ * 256-byte aligned, the same for every launch of one selection. All return MSIM_E_INVALID, with nothing written, for
+ * m == 0, no points, more than 65 535 points, no runs, more than 2^32 - 1 runs per point, n_ranks outside
+ * 1..MSIM_MAX_RANKS, pass >= MSIM_RANK_PASSES, a workspace that is too small, or a null pointer.
+ * begin: clears everything the later launches read (the workspace may hold anything before) and sets every row to
+ * {prefix 0, remaining = its rank}. `ranks` is host memory, n_ranks 0-based ranks in any order, duplicates allowed;
+ * they are copied into the call's arguments. A rank is not checked against the run count here (the launch does not
+ * know it): see msim_ranks_check and the step's status word. */
+int msim_rank_begin_launch(uint32_t m, uint32_t n_points, const uint64_t *ranks, uint32_t n_ranks, void *d_ws,
+                           size_t ws_bytes, void *stream);
+/* count, pass p: d_per_run / d_best_height as msim_moments_launch (n_points * runs_per_point records of m columns).
+ * Adds to the counts and never clears them, so several record buffers (chunks of runs, or other ranks through an
+ * all-reduce of msim_rank_counts_view) feed one pass. The workspace must be the one begin was given for the same m
+ * and n_points; a launch on any other does nothing. Ranks of a row group that still share a prefix have identical
+ * counts: only the lowest of them is counted (at pass 0, rank 0 alone) and the step reads its row for all of them.
+ * A test switch, MSIM_RANK_TEST_WG_RUNS=<n> (n > 0), read at every count launch: it only lowers the number of runs a
+ * workgroup takes (the smaller of the natural value and n), so a few hundred runs give several workgroups along
+ * the run axis. */
+int msim_rank_count_launch(uint32_t m, uint32_t n_points, uint64_t runs_per_point, const void *d_per_run,
+                           const void *d_best_height, uint32_t pass, void *d_ws, size_t ws_bytes, void *stream);
+/* step, pass p: narrows every row and clears the counts for the next pass. At the last pass (MSIM_RANK_PASSES - 1)
+ * d_out_or_NULL is required: n_points * m * 4 * n_ranks msim_order_stat in device memory, [point][column][quantity]
+ * [rank in the order given to begin]. d_status: one uint32_t in device memory that the launch ADDS to (clear it
+ * before the first pass): a row whose counts do not exceed what remains of its rank (a rank >= N) adds one per
+ * pass, keeps its state and writes no msim_order_stat; every other row is unaffected. */
+int msim_rank_step_launch(uint32_t m, uint32_t n_points, uint32_t pass, void *d_ws, size_t ws_bytes,
+                          void *d_out_or_NULL, void *d_status, void *stream);
+/* begin, then MSIM_RANK_PASSES x (count + step) over one record buffer. d_status is added to, as by the step. */
+int msim_rank_launch(uint32_t m, uint32_t n_points, uint64_t runs_per_point, const void *d_per_run,
+                     const void *d_best_height, const uint64_t *ranks, uint32_t n_ranks, void *d_out, void *d_status,
+                     void *d_ws, size_t ws_bytes, void *stream);
+/* Host only: MSIM_OK when ranks is not null, n_ranks lies in 1..MSIM_MAX_RANKS and every rank is below n_runs, else
+ * MSIM_E_INVALID. */
+int msim_ranks_check(uint64_t n_runs, const uint64_t *ranks, uint32_t n_ranks);
+/* Host conveniences shaped like msim_run_moments / msim_run_classes: out_stats and opt_sums per miner as msim_run's;
+ * out_order: [n_points][columns][4][n_ranks] msim_order_stat over all n_runs (runs_per_point) runs, columns = M, or
+ * n_classes with a class map (class_of_or_NULL: m entries checked with msim_classes_check; NULL with n_classes 0
+ * for per-miner columns). ranks are checked with msim_ranks_check against the total run count. The runs are
+ * simulated once, in chunks as msim_run_moments' (they follow MSIM_MOMENTS_CHUNK_RUNS); every chunk's records stay
+ * resident in a device buffer of their own until the eight passes are done (with a class map the folded records
+ * only; the per-miner chunk buffer is reused), and each pass counts every buffer, then steps once. That costs
+ * n_points * n_runs * (8 * columns + 4) bytes of device memory beside one chunk's launch buffers and the
+ * selection's workspace; an allocation that fails is MSIM_E_HIP. MSIM_E_CAPACITY on a failed run, as
+ * msim_run_moments. */
+int msim_run_order_stats(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                         const uint32_t *class_of_or_NULL, uint32_t n_classes, const uint64_t *ranks, uint32_t n_ranks,
+                         msim_stats *out_stats, msim_sums *opt_sums, msim_order_stat *out_order);
+int msim_sweep_run_order_stats(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point,
+                               uint32_t seed_base, int device, const uint32_t *class_of_or_NULL, uint32_t n_classes,
+                               const uint64_t *ranks, uint32_t n_ranks, msim_stats *out_stats, msim_sums *opt_sums,
+                               msim_order_stat *out_order);
 
 /* Convert fixed-point sums to MinerStats-style doubles. */
 void msim_sums_to_stats(const msim_sums *sums, uint32_t n, msim_stats *out);

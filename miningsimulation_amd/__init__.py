@@ -58,6 +58,15 @@ from .classes import (  # noqa: F401,E402
     report_classes,
 )
 
+from .quantiles import (  # noqa: F401,E402
+    OrderStat,
+    QuantileResult,
+    order_stats_from_words,
+    quantile_ci_ranks,
+    quantile_rank,
+    report_quantiles,
+)
+
 from . import model  # noqa: F401,E402  (first-order analytical stale-rate model, plot.py restated)
 
 __version__ = "0.1.0"

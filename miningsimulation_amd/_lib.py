@@ -75,8 +75,19 @@ EXPORTED = (
     "msim_classes_check",
     "msim_run_classes",
     "msim_sweep_run_classes",
+    "msim_rank_workspace_bytes",
+    "msim_rank_counts_view",
+    "msim_rank_begin_launch",
+    "msim_rank_count_launch",
+    "msim_rank_step_launch",
+    "msim_rank_launch",
+    "msim_ranks_check",
+    "msim_run_order_stats",
+    "msim_sweep_run_order_stats",
 )
 MSIM_CLASS_NONE = 0xFFFFFFFF
+MSIM_MAX_RANKS = 32
+MSIM_RANK_PASSES = 8
 
 
 class MsimTiming(ctypes.Structure):
@@ -183,6 +194,11 @@ class MsimContrast(ctypes.Structure):
         "stale_diff", "stale_diff_se", "stale_corr",
         "share_diff", "share_diff_se", "share_corr", "share_ratio", "share_ratio_se",
         "rate_diff", "rate_diff_se", "rate_corr")]
+
+
+class MsimOrderStat(ctypes.Structure):
+    """msim_order_stat: the r-th smallest key of a column, and how many keys lie below it and equal it."""
+    _fields_ = [("value", ctypes.c_uint64), ("below", ctypes.c_uint64), ("equal", ctypes.c_uint64)]
 
 
 def _load() -> ctypes.CDLL:
@@ -305,6 +321,26 @@ def _load() -> ctypes.CDLL:
     lib.msim_run_classes.restype = ctypes.c_int
     lib.msim_sweep_run_classes.argtypes = lib.msim_run_classes.argtypes
     lib.msim_sweep_run_classes.restype = ctypes.c_int
+    lib.msim_rank_workspace_bytes.argtypes = [u32, u32, u32]
+    lib.msim_rank_workspace_bytes.restype = sz
+    lib.msim_rank_counts_view.argtypes = [u32, u32, u32, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    lib.msim_rank_counts_view.restype = ctypes.c_int
+    lib.msim_rank_begin_launch.argtypes = [u32, u32, ctypes.POINTER(u64), u32, vp, sz, vp]
+    lib.msim_rank_begin_launch.restype = ctypes.c_int
+    lib.msim_rank_count_launch.argtypes = [u32, u32, u64, vp, vp, u32, vp, sz, vp]
+    lib.msim_rank_count_launch.restype = ctypes.c_int
+    lib.msim_rank_step_launch.argtypes = [u32, u32, u32, vp, sz, vp, vp, vp]
+    lib.msim_rank_step_launch.restype = ctypes.c_int
+    lib.msim_rank_launch.argtypes = [u32, u32, u64, vp, vp, ctypes.POINTER(u64), u32, vp, vp, vp, sz, vp]
+    lib.msim_rank_launch.restype = ctypes.c_int
+    lib.msim_ranks_check.argtypes = [u64, ctypes.POINTER(u64), u32]
+    lib.msim_ranks_check.restype = ctypes.c_int
+    lib.msim_run_order_stats.argtypes = [vp, u64, u64, u32, ctypes.c_int, ctypes.POINTER(u32), u32,
+                                         ctypes.POINTER(u64), u32, ctypes.POINTER(MsimStats),
+                                         ctypes.POINTER(MsimSums), ctypes.POINTER(MsimOrderStat)]
+    lib.msim_run_order_stats.restype = ctypes.c_int
+    lib.msim_sweep_run_order_stats.argtypes = lib.msim_run_order_stats.argtypes
+    lib.msim_sweep_run_order_stats.restype = ctypes.c_int
     lib.msim_version.argtypes = []
     lib.msim_version.restype = ctypes.c_char_p
     return lib

@@ -261,3 +261,91 @@ def _run_sharded_moments(sim, n_total, seed_base, run_begin, stream, launch, lau
         moments=moments_from_words(host[o_mom:o_hist].view(mc, MOMENT_WORDS).numpy()),
         hist=host[o_hist:o_cross].view(mc, 2, row).numpy().astype("uint64") if hist is not None else None,
     ), cross
+
+
+def run_sharded_quantiles(sim, n_total: int, seed_base: int, qs=(0.05, 0.5, 0.95), ranks=None, run_begin: int = 0,
+                          stream=None, launch: Optional[Callable] = None, launch_rank_begin: Optional[Callable] = None,
+                          launch_rank_count: Optional[Callable] = None, launch_rank_step: Optional[Callable] = None,
+                          device=None, max_chunk: int = MAX_LAUNCH_RUNS):
+    """run_sharded plus the exact order statistics of the per-run terms over ALL n_total runs (quantiles.py): this
+    rank's shard runs through msim_launch in chunks whose records stay resident in device buffers of their own; then
+    msim_rank_begin_launch and, per pass, msim_rank_count_launch on every buffer, ONE all-reduce of the workspace's
+    counts view, and msim_rank_step_launch. Ranks (quantile_rank of `qs`, or `ranks` as given) are relative to
+    n_total. The digit counts are integer sums over runs and every rank steps on the same totals, so the result is
+    identical on every rank and for every world size. The sums and status words travel behind the counts in the
+    first pass's all-reduce: eight all-reduces per job.
+
+    Returns a QuantileResult (points = [the SimulationResult of run_sharded's sums], order[0][miner][quantity][j]).
+    `launch` / `launch_rank_begin` / `launch_rank_count` / `launch_rank_step` replace sim.launch and
+    sim.launch_rank_* (same signatures, workspace None for the launch) so that the partition, the resident buffers
+    and the eight all-reduces can be exercised on CPU ranks with a gloo group."""
+    import contextlib
+
+    import torch
+    import torch.distributed as dist
+
+    from ._lib import MsimSums
+    from .quantiles import (RANK_PASSES, QuantileResult, order_stats_from_words, rank_counts_view, rank_workspace_bytes,
+                            ranks_array, ranks_of)
+    from .simulation import SimulationResult, sums_to_stats
+
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    begin, n = shard(n_total, world, rank)
+    m = len(sim.miners)
+    sel = ranks_of(n_total, qs, ranks)
+    ranks_array(sel, n_total)  # ValueError for a rank that is not below n_total
+    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    ws_words = rank_workspace_bytes(m, 1, len(sel)) // 8
+    c_off, c_words = rank_counts_view(m, 1, len(sel))
+    assert c_off % 8 == 0 and c_off // 8 + c_words == ws_words  # the counts end the workspace
+    # the workspace with the sums and the two status words behind its counts: they join the first all-reduce
+    buf = torch.zeros(ws_words + 6 * m + 2, dtype=torch.int64, device=dev)
+    d_ws = buf[:ws_words]
+    sums = buf[ws_words:ws_words + 6 * m].view(m, 6)
+    status = buf[ws_words + 6 * m:]
+    part = torch.zeros((m, 6), dtype=torch.int64, device=dev)
+    pst = torch.zeros(2, dtype=torch.int32, device=dev)
+    out = torch.zeros((m, 4, len(sel), 3), dtype=torch.int64, device=dev)
+    rst = torch.zeros(1, dtype=torch.int32, device=dev)
+    chunk = min(n, max_chunk)
+    ws = None
+    if n and launch is None:
+        ws = torch.empty(sim.workspace_bytes(chunk), dtype=torch.uint8, device=dev)
+    kept = []
+    ctx = torch.cuda.stream(stream) if (stream is not None and dev.type == "cuda") else contextlib.nullcontext()
+    if stream is not None and dev.type == "cuda":
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    with ctx:
+        for off in range(0, n, max(chunk, 1)):
+            cn = min(chunk, n - off)
+            rec = torch.zeros((cn, m, 2), dtype=torch.int32, device=dev)
+            bh = torch.zeros(cn, dtype=torch.int32, device=dev)
+            (launch or sim.launch)(cn, run_begin + begin + off, seed_base, part, ws, pst, d_per_run=rec,
+                                   d_best_height=bh, stream=stream)
+            sums += part
+            status += pst
+            kept.append((cn, rec, bh))
+        (launch_rank_begin or sim.launch_rank_begin)(sel, d_ws, stream=stream)
+        for p in range(RANK_PASSES):
+            for cn, rec, bh in kept:
+                (launch_rank_count or sim.launch_rank_count)(cn, rec, bh, p, d_ws, stream=stream)
+            if world > 1:
+                dist.all_reduce(buf[c_off // 8:] if p == 0 else buf[c_off // 8:ws_words])
+            (launch_rank_step or sim.launch_rank_step)(p, d_ws, out, rst, stream=stream)
+    if stream is not None and dev.type == "cuda":
+        torch.cuda.current_stream(dev).wait_stream(stream)
+    host = buf[ws_words:].cpu()
+    if int(host[6 * m + 1]) != 0:
+        raise RuntimeError(f"{int(host[6 * m + 1])} runs exceeded the compact state capacity")
+    if int(rst.cpu()[0]) != 0:
+        raise RuntimeError("a rank was not below the run count")
+    rows = host[:6 * m].view(m, 6).tolist()
+    u64 = (lambda v: int(v) & 0xFFFFFFFFFFFFFFFF)
+    res = SimulationResult(
+        stats_total=sums_to_stats([[u64(x) for x in r] for r in rows]),
+        sums=[MsimSums(r[0], r[1], u64(r[2]), u64(r[3]), u64(r[4]), u64(r[5])) for r in rows],
+        n_runs=n_total,
+    )
+    return QuantileResult(points=[res], ranks=sel, qs=None if ranks is not None else [float(q) for q in qs],
+                          order=order_stats_from_words(out.cpu().numpy(), 1, m, len(sel)), n_runs=n_total)

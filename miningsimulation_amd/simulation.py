@@ -25,6 +25,8 @@ from ._lib import (MSIM_SWEEP_SHARED_DRAWS, MsimCross, MsimMiner, MsimMoments, M
 from .classes import class_count, class_map_struct
 from .contrasts import CROSS_WORDS, Pair, cross_from_words, pairs_struct
 from .moments import MOMENT_WORDS, HistSpec, moments_from_words
+from .quantiles import (QuantileResult, _launch_rank_begin, _launch_rank_count, _launch_rank_step, _run_quantiles,
+                        rank_counts_view, rank_workspace_bytes)
 
 SIM_DURATION_MS = 31_556_952_000  # main.cpp:7 std::chrono::months{12}
 SIM_RUNS = 16 * 2048              # main.cpp:10
@@ -348,6 +350,39 @@ class Simulation:
         and launch_cross of a Simulation of n_classes miners read d_class_run as they read d_per_run."""
         _launch_fold(len(self.miners), 1, n_runs, d_per_run, d_class_of, n_classes, d_class_run, stream)
 
+    def run_quantiles(self, n_runs: int, qs: Sequence[float] = (0.05, 0.5, 0.95), ranks: Optional[Sequence[int]] = None,
+                      class_of: Optional[Sequence[int]] = None, n_classes: Optional[int] = None, run_begin: int = 0,
+                      seed_base: int = DEFAULT_SEED_BASE, device: int = 0) -> QuantileResult:
+        """msim_run_order_stats: run() plus the exact order statistics of the per-run found, stale, share and rate
+        terms of every miner (of every class with a class map) at the quantiles `qs` (quantile_rank), or at the
+        0-based `ranks` when given; the per-run records never leave device memory. result.order[0][column]
+        [quantity][j] is an OrderStat (value, below, equal) of Python ints; result.values scales them."""
+        return _run_quantiles(lib.msim_run_order_stats, "msim_run_order_stats", self._h, 1, len(self.miners), n_runs,
+                              qs, ranks, class_of, n_classes, run_begin, seed_base, device)
+
+    def rank_workspace_bytes(self, n_ranks: int, columns: Optional[int] = None) -> int:
+        """msim_rank_workspace_bytes for this network's columns (`columns`: the class count of folded records)."""
+        return rank_workspace_bytes(columns or len(self.miners), 1, n_ranks)
+
+    def rank_counts_view(self, n_ranks: int, columns: Optional[int] = None):
+        """msim_rank_counts_view: (byte offset, uint64 words) of the counts inside the workspace."""
+        return rank_counts_view(columns or len(self.miners), 1, n_ranks)
+
+    def launch_rank_begin(self, ranks: Sequence[int], d_ws, stream=None, columns: Optional[int] = None) -> None:
+        """msim_rank_begin_launch on the current device: d_ws uint8 [rank_workspace_bytes(len(ranks))] or larger."""
+        _launch_rank_begin(columns or len(self.miners), 1, ranks, d_ws, stream)
+
+    def launch_rank_count(self, n_runs: int, d_per_run, d_best_height, pass_: int, d_ws, stream=None,
+                          columns: Optional[int] = None) -> None:
+        """msim_rank_count_launch of pass `pass_` over a launch's records (as launch_moments reads them); it adds to
+        the workspace's counts, so several record buffers feed one pass."""
+        _launch_rank_count(columns or len(self.miners), 1, n_runs, d_per_run, d_best_height, pass_, d_ws, stream)
+
+    def launch_rank_step(self, pass_: int, d_ws, d_out, d_status, stream=None, columns: Optional[int] = None) -> None:
+        """msim_rank_step_launch of pass `pass_`: d_out int64 [M, 4, n_ranks, 3] (required at the last pass, else it
+        may be None), d_status int32 [1] (added to)."""
+        _launch_rank_step(columns or len(self.miners), 1, pass_, d_ws, d_out, d_status, stream)
+
     def run_multi(self, n_runs: int, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
                   devices: Sequence[int] = (0,)) -> SimulationResult:
         """msim_run_multi: the runs sharded over `devices` (one host thread each) and combined with one RCCL
@@ -540,6 +575,34 @@ class Sweep:
                     stream=None) -> None:
         """msim_fold_launch over a sweep launch's records; d_class_run int32 [n_points, runs_per_point, n_classes, 2]."""
         _launch_fold(self.m, len(self.sims), runs_per_point, d_per_run, d_class_of, n_classes, d_class_run, stream)
+
+    def run_quantiles(self, runs_per_point: int, qs: Sequence[float] = (0.05, 0.5, 0.95),
+                      ranks: Optional[Sequence[int]] = None, class_of: Optional[Sequence[int]] = None,
+                      n_classes: Optional[int] = None, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
+                      device: int = 0) -> QuantileResult:
+        """msim_sweep_run_order_stats: Simulation.run_quantiles over a sweep; result.order[point][column][quantity][j]."""
+        return _run_quantiles(lib.msim_sweep_run_order_stats, "msim_sweep_run_order_stats", self._h, len(self.sims),
+                              self.m, runs_per_point, qs, ranks, class_of, n_classes, run_begin, seed_base, device)
+
+    def rank_workspace_bytes(self, n_ranks: int, columns: Optional[int] = None) -> int:
+        return rank_workspace_bytes(columns or self.m, len(self.sims), n_ranks)
+
+    def rank_counts_view(self, n_ranks: int, columns: Optional[int] = None):
+        return rank_counts_view(columns or self.m, len(self.sims), n_ranks)
+
+    def launch_rank_begin(self, ranks: Sequence[int], d_ws, stream=None, columns: Optional[int] = None) -> None:
+        """msim_rank_begin_launch for a sweep launch's records (every point selects the same ranks)."""
+        _launch_rank_begin(columns or self.m, len(self.sims), ranks, d_ws, stream)
+
+    def launch_rank_count(self, runs_per_point: int, d_per_run, d_best_height, pass_: int, d_ws, stream=None,
+                          columns: Optional[int] = None) -> None:
+        """msim_rank_count_launch over a sweep launch's records."""
+        _launch_rank_count(columns or self.m, len(self.sims), runs_per_point, d_per_run, d_best_height, pass_, d_ws,
+                           stream)
+
+    def launch_rank_step(self, pass_: int, d_ws, d_out, d_status, stream=None, columns: Optional[int] = None) -> None:
+        """msim_rank_step_launch; d_out int64 [n_points, M, 4, n_ranks, 3]."""
+        _launch_rank_step(columns or self.m, len(self.sims), pass_, d_ws, d_out, d_status, stream)
 
     def workspace_bytes(self, runs_per_point: int) -> int:
         return int(lib.msim_sweep_workspace_bytes(self._h, runs_per_point))
