@@ -40,6 +40,15 @@ extern "C" {
 #define MSIM_E_CAPACITY (-6) /* a run outgrew every window of the general engine (its last window holds every
                                 block a run of the config's duration can have: practically never) */
 #define MSIM_E_PICK (-7)     /* PickFinder fell through (simulation.h:220 assert): percentages < 100 */
+/* Durations. Any duration_ms >= 0 is accepted and exact; what changes with it is the engine. The event-skipping
+ * pipeline cuts a run into at most 256 draw segments of at most 65 504 blocks (its draw kernel packs a segment's
+ * per-miner counts into 16 bits, and one miner can own every block of a segment), so it serves honest networks up to
+ * about 318 years (256 x 65 504 blocks at one per 600 s, less the 8-sigma margin of the pre-generated blocks). A
+ * longer run is not refused: msim_config_create keeps it on the per-lane kernel (msim_pipeline_info: uses_pipeline 0,
+ * as under MSIM_NO_PIPELINE), slower and exact; a shared-draw sweep of such points runs as the plain sweep. No plan
+ * ever has a segment of more than 65 535 blocks, whatever the run count, the wave slots or the launches in flight.
+ * The general engine refuses (MSIM_E_MINERS) a selfish network whose last window, every block a run can have, would
+ * pass 96 GiB of chains for one lane or 2^32 blocks (about 81 000 years). */
 
 #define MSIM_MAX_MINERS 15        /* networks on the compact per-lane / entity-engine state */
 #define MSIM_MAX_SELFISH 4        /* selfish miners per network on the entity engine (msim_sel.h); more run on
@@ -144,7 +153,13 @@ int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t du
  *   MSIM_GEN_TEST_LIST_CAP=<n> (n >= 1)  the length of the tier lists that the kernels are told; the lists keep their
  *                                        natural allocation. A run that finds no room in a list fails in the same way
  * msim_pipeline_info reports the lowered geometry (slice_runs: tier-1 lanes, segment_blocks: tier-1 window,
- * blocks_per_run: last window). Unset, nothing changes. */
+ * blocks_per_run: last window). Unset, nothing changes.
+ * MSIM_K1_SLOTS=<n>, read at every sizing and launch call of the honest pipeline (single networks and shared-draw
+ * sweeps): the draw kernel's wave slots, in place of the device's (compute units x resident waves), for which the
+ * run is cut into segments. One launch in flight plans for 3 n slots, j launches for 2 n / j. A measurement switch
+ * and a test switch: 1 with two launches in flight gives the fewest, longest segments the planner lays out
+ * (tests/test_gpu_long_runs.py), and a pinned value makes msim_pipeline_info independent of the device
+ * (tests/host_plans.py). It changes the geometry and the workspace size, never a result. */
 int msim_config_is_wide(const msim_config *cfg);
 /* How many launches of this config the caller keeps in flight at once (default 1; e.g. 2 when steps
  * alternate over two HIP streams). The event-skipping pipeline plans its draw kernel's grid for it: three

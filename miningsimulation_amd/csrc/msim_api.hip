@@ -247,7 +247,7 @@ msim::PipeLimits pipe_test_limits(bool point)
 // K1 wave slots of the current device (CUs x resident K1 waves per CU); 8192 if it cannot be queried.
 uint32_t draw_slots()
 {
-    if (const char *e = getenv("MSIM_K1_SLOTS")) return (uint32_t)atoi(e);  // A/B override (measurement only)
+    if (const char *e = getenv("MSIM_K1_SLOTS")) return (uint32_t)atoi(e);  // measurement and test switch (msim.h)
     int dev = 0, cus = 0, blocks = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         msim::draws_blocks_per_cu(&blocks) != hipSuccess || cus <= 0 || blocks <= 0)
@@ -873,7 +873,10 @@ int config_create_impl(const msim_miner *miners, uint32_t n, int64_t duration_ms
         // the draw kernel's fast threshold holds delays below FTHR_CAP (262 s; msim_fastdraw.h)
         bool prop_ok = true;
         for (uint32_t k = 0; k < n; ++k) prop_ok = prop_ok && miners[k].propagation_ms < (int64_t)msim::FTHR_CAP;
-        c->pipe_ok = !sel && !gen && prop_ok && rho <= PIPE_MAX_RHO && getenv("MSIM_NO_PIPELINE") == nullptr;
+        // a run longer than the draw kernel's 256 workers of 65 504 blocks cover (msim_pipeline.h pipe_fits, ~318
+        // years) stays on the per-lane kernel
+        c->pipe_ok = !sel && !gen && prop_ok && rho <= PIPE_MAX_RHO && msim::pipe_fits(duration_ms) &&
+                     getenv("MSIM_NO_PIPELINE") == nullptr;
     } else {
         c->wide = true;
         c->pipe_ok = false;

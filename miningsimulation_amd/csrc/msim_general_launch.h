@@ -70,13 +70,15 @@ inline bool gen_needs_full(bool selfish, int64_t max_prop_ms)
     return mu + 10.0 * sqrt(mu > 1.0 ? mu : 1.0) + 64.0 >= 1024.0;
 }
 inline double gen_lane_bytes(uint32_t max_m, uint32_t cap) { return (double)max_m * (cap * 12.0 + 12.0); }
-inline uint32_t gen_last_cap(int64_t max_duration)
+inline uint64_t gen_last_blocks(int64_t max_duration)
 {
     const double mu = (double)max_duration / 599999.5, sd = sqrt(mu > 1.0 ? mu : 1.0);
     uint64_t top = (uint64_t)ceil(mu + 10.0 * sd + 64.0) + 2;
     top = (top + 255) / 256 * 256;
-    return (uint32_t)(top > 4096 ? top : 4096);
+    return top > 4096 ? top : 4096;
 }
+// The last window as the 32-bit block count the tiers hold; gen_fits refuses a duration whose window does not fit it.
+inline uint32_t gen_last_cap(int64_t max_duration) { return (uint32_t)gen_last_blocks(max_duration); }
 //
 // GenLimits: test switches (MSIM_GEN_TEST_*, include/msim.h; 0: none) that only LOWER a limit, so that a few hundred
 // short runs reach what the natural geometry reaches with year-long selfish majorities or not at all: a lane that
@@ -111,6 +113,9 @@ inline int gen_tiers(uint32_t max_m, int64_t max_duration, double budget, GenTie
 // Whether G can hold a network of m miners and runs of duration_ms (one lane of its last window).
 inline bool gen_fits(uint32_t m, int64_t duration_ms, bool full)
 {
+    // a last window of 2^32 blocks or more (about 81 000 years) would wrap gen_last_cap: for one or two miners its
+    // chains are still below GEN_MAX_LANE_BYTES at 12 B a block
+    if (full && gen_last_blocks(duration_ms) > 0xFFFFFFFFull) return false;
     return gen_lane_bytes(m, full ? gen_last_cap(duration_ms) : 4096u) <= GEN_MAX_LANE_BYTES;
 }
 

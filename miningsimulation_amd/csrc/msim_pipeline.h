@@ -159,26 +159,49 @@ inline double pipe_need(int64_t duration_ms)
     return mu + 8.0 * sd + 64.0;
 }
 
+// The longest segment a plan may have. K1 packs a segment's per-owner counts as u16 pairs (CNT_WORDS; DevCtx::packed in
+// msim_drawgen.hip, `c & 0xFFFFu` / `c >> 16` in combine_run), and one miner can own every block of a segment, so a
+// segment holds at most 65 535 blocks: the largest multiple of GROUP below that.
+constexpr uint32_t PIPE_MAX_SEG = 0xFFFFu / GROUP * GROUP;
+constexpr uint32_t PIPE_MAX_WORKERS = 256;
+
+// Whether PIPE_MAX_WORKERS workers of at most PIPE_MAX_SEG blocks cover a run of this duration (up to ~318 years).
+// The pipeline takes no longer run: msim_config_create sends it to the per-lane kernel.
+inline bool pipe_fits(int64_t duration_ms)
+{
+    return ceil(pipe_need(duration_ms) / PIPE_MAX_WORKERS / GROUP) * GROUP <= (double)PIPE_MAX_SEG;
+}
+
 // Workers per run for a slice of nr runs on `slots` wave slots: minimise rounds(w) * (seg(w) + jump cost), jump ~ 25
-// blocks of work.
+// blocks of work. When that choice makes segments longer than PIPE_MAX_SEG (few wave slots, many runs, long runs: the
+// grid is full with few workers), the same minimum over the worker counts whose segments fit; a plan whose segments
+// fit is what it always was.
 inline uint32_t pipe_workers(int64_t duration_ms, uint32_t nr, uint32_t slots)
 {
     const double need = pipe_need(duration_ms);
     const double rows = nr / 64.0;
     if (slots < 1) slots = 1;
-    uint32_t best_w = 1;
-    double best_f = 1e300;
-    for (uint32_t w = 1; w <= 256; ++w) {
-        const uint32_t sg = (uint32_t)ceil(need / w / GROUP) * GROUP;
-        if (sg < MIN_SEG && w > 1) break;
-        const double rounds = ceil(rows * w / slots);
-        const double f = rounds * (sg + 25.0);
-        if (f < best_f * 0.999) {
-            best_f = f;
-            best_w = w;
+    auto seg_of = [&](uint32_t w) { return (uint32_t)ceil(need / w / GROUP) * GROUP; };
+    auto best_from = [&](uint32_t w0) {
+        uint32_t best_w = w0;
+        double best_f = 1e300;
+        for (uint32_t w = w0; w <= PIPE_MAX_WORKERS; ++w) {
+            const uint32_t sg = seg_of(w);
+            if (sg < MIN_SEG && w > w0) break;
+            const double rounds = ceil(rows * w / slots);
+            const double f = rounds * (sg + 25.0);
+            if (f < best_f * 0.999) {
+                best_f = f;
+                best_w = w;
+            }
         }
-    }
-    return best_w;
+        return best_w;
+    };
+    const uint32_t w = best_from(1);
+    if (seg_of(w) <= PIPE_MAX_SEG) return w;
+    uint32_t w0 = (uint32_t)ceil(need / PIPE_MAX_SEG);  // the fewest workers whose segments fit
+    while (w0 < PIPE_MAX_WORKERS && seg_of(w0) > PIPE_MAX_SEG) ++w0;
+    return best_from(w0 < PIPE_MAX_WORKERS ? w0 : PIPE_MAX_WORKERS);
 }
 
 // The layout of a slice of exactly nr runs (a multiple of 256) cut into nseg workers per run: K2's episode records,
