@@ -43,6 +43,13 @@
 // for a sweep); in --json output a "quantiles" object with the ranks and, per column and quantity (found, stale,
 // share, rate; the last two in units of 2^-32), [value, below, equal] per rank.
 //
+// --tails Q (anywhere on the command line; composes with every other option): the lower tail of every miner's own
+// share at the quantile Q (msim_run_tails / msim_sweep_run_tails, one GPU, one more pass over the runs): the blocks
+// found, share and stale rate averaged over the miner's worst k = max(1, ceil(Q runs)) runs by share, ties at the
+// quantile weighted equally, next to the all-runs means. One line per miner (per class with --classes, per point for
+// a sweep); in --json output a "tails" object with the rank, k and per column a "tail" entry: the threshold, the run
+// counts below and at it, the four tail means and the all-runs means.
+//
 // Build: make -C host
 // "c5" runs BASELINE configs[4] (2 pools + 1 024 small miners, integer weights summing to
 // W = 102 400, msim_config_create_weighted), which the reference's integer percentages cannot express.
@@ -322,6 +329,83 @@ static std::string JsonQuantiles(const Quantiles &qs, size_t point, bool classes
     return s + "]}";
 }
 
+// --tails Q: the lower tail of every column's own share at the quantile Q (msim_run_tails with one spec per column
+// and point, each conditioned on itself): the order statistics, the columns' total moments and the tails,
+// [point][column].
+struct Tails {
+    double q = -1.0;
+    uint64_t rank = 0, runs = 0;
+    uint32_t cols = 0;
+    std::vector<msim_order_stat> order;  // [point][column][4][1]
+    std::vector<msim_moments> total;
+    std::vector<msim_tail> tails;
+    std::vector<msim_tail_spec> specs;
+    bool on() const { return q >= 0.0; }
+    void Set(uint64_t n_runs, uint32_t columns, size_t points)
+    {
+        runs = n_runs;
+        cols = columns;
+        const double k = std::ceil(q * (double)n_runs);  // hist_quantile's k
+        rank = k < 1.0 ? 0 : (uint64_t)k - 1;
+        order.resize(points * cols * 4);
+        total.resize(points * cols);
+        tails.resize(points * cols);
+        specs.clear();
+        for (uint32_t p = 0; p < points; ++p)
+            for (uint32_t c = 0; c < cols; ++c) specs.push_back({p, c, 2, 0, p, c});
+    }
+    // the means over the worst k = rank + 1 runs and over all runs of one column
+    void Means(size_t point, size_t col, double mu[4], msim_errors *all) const
+    {
+        const size_t i = point * cols + col;
+        if (msim_tail_means(&tails[i], &total[i], runs, rank + 1, 0, mu) != MSIM_OK) mu[0] = mu[1] = mu[2] = mu[3] = NAN;
+        msim_moments_to_errors(&total[i], 1, runs, all);
+    }
+};
+
+// One line per miner, or per class (tails.report_tails in the package; the text behind the head is
+// tails.tail_columns).
+static void PrintTails(const Tails &t, size_t point, const std::vector<Miner> &miners, const Classes *classes,
+                       uint64_t total_weight)
+{
+    for (size_t c = 0; c < t.cols; ++c) {
+        if (classes)
+            std::printf("  - Class %zu (%u miners, %g%% of network hashrate)", c, classes->members[c],
+                        (double)classes->weight[c] * 100.0 / (double)total_weight);
+        else
+            std::printf("  - Miner %u (%llu%% of network hashrate)", miners[c].id, (unsigned long long)miners[c].perc);
+        double mu[4];
+        msim_errors all;
+        t.Means(point, c, mu, &all);
+        std::printf(" in its worst %llu of %llu runs found %g blocks (all runs: %g) i.e. %g%% of blocks (%g%%)."
+                    " Stale rate: %g%% (%g%%).\n",
+                    (unsigned long long)(t.rank + 1), (unsigned long long)t.runs, mu[0], all.found_mean, mu[2] * 100,
+                    all.share_mean * 100, mu[3] * 100, all.rate_mean * 100);
+    }
+}
+
+static std::string JsonTails(const Tails &t, size_t point, bool classes)
+{
+    char buf[512];
+    std::snprintf(buf, sizeof(buf), ", \"tails\": {\"columns\": \"%s\", \"q\": %.17g, \"rank\": %llu, \"k\": %llu, \"tail\": [",
+                  classes ? "classes" : "miners", t.q, (unsigned long long)t.rank, (unsigned long long)(t.rank + 1));
+    std::string s = buf;
+    for (size_t c = 0; c < t.cols; ++c) {
+        const size_t i = point * t.cols + c;
+        double mu[4];
+        msim_errors all;
+        t.Means(point, c, mu, &all);
+        std::snprintf(buf, sizeof(buf),
+                      "%s{\"value\": %llu, \"n_below\": %llu, \"n_equal\": %llu, \"found\": %.17g, \"stale\": %.17g, "
+                      "\"share\": %.17g, \"rate\": %.17g, \"all_runs\": {\"found\": %.17g, \"share\": %.17g, \"rate\": %.17g}}",
+                      c ? ", " : "", (unsigned long long)t.order[i * 4 + 2].value, (unsigned long long)t.tails[i].n_below,
+                      (unsigned long long)t.tails[i].n_equal, mu[0], mu[1], mu[2], mu[3], all.found_mean, all.share_mean,
+                      all.rate_mean);
+        s += buf;
+    }
+    return s + "]}";
+}
+
 // One JSON line for a point: the network and its per-miner averages (the report's numbers).
 static void PrintJsonNumber(const char *sep, const char *name, double v)
 {
@@ -391,7 +475,7 @@ static void PrintJson(size_t point, const std::vector<Miner> &miners, const std:
         }
         std::printf("]");
     }
-    std::printf("%s}\n", tail.c_str());  // --quantiles: its object
+    std::printf("%s}\n", tail.c_str());  // --quantiles and --tails: their objects
 }
 
 // RCCL prints a version banner on stdout when a communicator is created. The report on stdout must keep
@@ -439,6 +523,7 @@ struct SweepSpec {
     bool errors = false;
     bool classes = false;  // --classes: statistics per class of identical miners (of the first point)
     Quantiles quantiles;   // --quantiles Q1,Q2,..
+    Tails tails;           // --tails Q
     long long contrast = -1;  // --contrast P: the baseline point, or -1
     bool shared_draws = false;  // --shared-draws: msim_sweep_create_ex(MSIM_SWEEP_SHARED_DRAWS)
 };
@@ -579,6 +664,17 @@ static int RunSweep(const SweepSpec &sp)
                                               again.data(), nullptr, qs.order.data());
         });
     }
+    Tails tl = sp.tails;
+    if (rc == MSIM_OK && tl.on()) {  // and one for the tails: the selection, then the tail launches on the same records
+        if (sp.classes && cls.class_of.empty()) cls = GroupMiners(sp.points[0]);
+        tl.Set(sp.runs, sp.classes ? cls.n() : m, sp.points.size());
+        std::vector<msim_stats> again(st.size());
+        rc = WithStdoutOnStderr([&] {
+            return msim_sweep_run_tails(sw, 0, sp.runs, sp.seed_base, 0, sp.classes ? cls.class_of.data() : nullptr,
+                                        sp.classes ? cls.n() : 0, &tl.rank, 1, tl.specs.data(), (uint32_t)tl.specs.size(),
+                                        again.data(), nullptr, tl.order.data(), tl.total.data(), tl.tails.data());
+        });
+    }
     if (rc == MSIM_OK) {
         const long long days = sp.duration_ms / 86'400'000;
         for (size_t p = 0; p < sp.points.size(); ++p) {
@@ -590,7 +686,8 @@ static int RunSweep(const SweepSpec &sp)
                 pc = con.data() + (p - (p > (size_t)sp.contrast)) * cols;
             const msim_errors *ce = sp.classes ? cerrs.data() + p * cls.n() : nullptr;
             if (sp.json) {
-                const std::string tail = qs.on() ? JsonQuantiles(qs, p, sp.classes) : std::string();
+                const std::string tail = (qs.on() ? JsonQuantiles(qs, p, sp.classes) : std::string()) +
+                                         (tl.on() ? JsonTails(tl, p, sp.classes) : std::string());
                 if (sp.classes)
                     PrintJson(p, sp.points[p], ps, sp.runs, sp.total_weight, pe, nullptr, &cls, ce, pc, tail);
                 else
@@ -601,6 +698,7 @@ static int RunSweep(const SweepSpec &sp)
                 if (sp.classes) PrintClasses(cls, ce, sp.total_weight);
                 if (pc) PrintContrasts(p, (size_t)sp.contrast, pc, cols, sp.classes ? "Class" : "Miner");
                 if (qs.on()) PrintQuantiles(qs, p, sp.points[p], sp.classes ? &cls : nullptr, sp.total_weight);
+                if (tl.on()) PrintTails(tl, p, sp.points[p], sp.classes ? &cls : nullptr, sp.total_weight);
             }
         }
     }
@@ -614,6 +712,7 @@ int main(int argc, char **argv)
     bool errors = false;   // --errors, wherever it stands; the other arguments keep their positions
     bool classes = false;  // --classes, likewise
     Quantiles quantiles;   // --quantiles Q1,Q2,.., likewise
+    Tails tails;           // --tails Q, likewise
     {
         int kept = 1;
         for (int i = 1; i < argc; ++i) {
@@ -622,6 +721,13 @@ int main(int argc, char **argv)
                     quantiles = ParseQuantiles(argv[++i]);
                 } catch (const std::exception &e) {
                     std::fprintf(stderr, "msim_main: %s\n", e.what());
+                    return 2;
+                }
+            } else if (std::string(argv[i]) == "--tails" && i + 1 < argc) {
+                char *end = nullptr;
+                tails.q = std::strtod(argv[++i], &end);
+                if (end == argv[i] || *end || !(tails.q >= 0.0 && tails.q <= 1.0)) {
+                    std::fprintf(stderr, "msim_main: --tails Q: Q within [0, 1]\n");
                     return 2;
                 }
             } else if (std::string(argv[i]) == "--errors")
@@ -661,6 +767,7 @@ int main(int argc, char **argv)
             sp.errors = errors;
             sp.classes = classes;
             sp.quantiles = quantiles;
+            sp.tails = tails;
             if (sp.contrast >= (long long)sp.points.size())
                 throw std::runtime_error("--contrast " + std::to_string(sp.contrast) + ": there are " +
                                          std::to_string(sp.points.size()) + " points");
@@ -746,10 +853,21 @@ int main(int argc, char **argv)
             }))
             return die("msim_run_order_stats", rc);
     }
+    if (tails.on()) {  // and one for the tails
+        tails.Set(sim_runs, classes ? cls.n() : (uint32_t)miners.size(), 1);
+        std::vector<msim_stats> again(miners.size());
+        if (int rc = WithStdoutOnStderr([&] {
+                return msim_run_tails(cfg, 0, sim_runs, seed_base, 0, classes ? cls.class_of.data() : nullptr,
+                                      classes ? cls.n() : 0, &tails.rank, 1, tails.specs.data(), (uint32_t)tails.specs.size(),
+                                      again.data(), nullptr, tails.order.data(), tails.total.data(), tails.tails.data());
+            }))
+            return die("msim_run_tails", rc);
+    }
     if (json) {
         PrintJson(0, miners, stats_total, sim_runs, total_weight, errors ? errs.data() : nullptr, nullptr,
                   classes ? &cls : nullptr, classes ? cerrs.data() : nullptr, nullptr,
-                  quantiles.on() ? JsonQuantiles(quantiles, 0, classes) : std::string());
+                  (quantiles.on() ? JsonQuantiles(quantiles, 0, classes) : std::string()) +
+                      (tails.on() ? JsonTails(tails, 0, classes) : std::string()));
         msim_config_destroy(cfg);
         return 0;
     }
@@ -759,6 +877,7 @@ int main(int argc, char **argv)
     PrintReport(miners, stats_total, sim_runs, total_weight, (long long)days.count(), errors ? errs.data() : nullptr);
     if (classes) PrintClasses(cls, cerrs.data(), total_weight);
     if (quantiles.on()) PrintQuantiles(quantiles, 0, miners, classes ? &cls : nullptr, total_weight);
+    if (tails.on()) PrintTails(tails, 0, miners, classes ? &cls : nullptr, total_weight);
     msim_config_destroy(cfg);
     return 0;
 }

@@ -121,6 +121,8 @@ int msim_config_create_weighted(const msim_miner *miners, uint32_t n, int64_t du
  * chunk loop and its limb-by-limb addition. msim_run_order_stats and msim_sweep_run_order_stats follow it too.
  * MSIM_RANK_TEST_WG_RUNS=<n> (n > 0), read at every msim_rank_count_launch: a workgroup of the count kernel takes at
  * most n runs, so a few hundred runs give several workgroups along the run axis (see msim_rank_count_launch).
+ * MSIM_TAIL_TEST_WG_RUNS=<n> (n > 0) does the same for msim_tail_launch, and msim_run_tails and msim_sweep_run_tails
+ * follow MSIM_MOMENTS_CHUNK_RUNS.
  * Five more, MSIM_PIPE_TEST_*, read at every sizing and launch call of the honest pipeline (single networks and
  * shared-draw sweeps). Each only ever lowers a capacity below its 8-sigma size (the smaller of the natural value and
  * n, n > 0), and does so in the layout computation, so the buffers are exactly as large as the kernels are told:
@@ -621,6 +623,99 @@ int msim_sweep_run_order_stats(const msim_sweep *sweep, uint64_t run_begin, uint
                                uint32_t seed_base, int device, const uint32_t *class_of_or_NULL, uint32_t n_classes,
                                const uint64_t *ranks, uint32_t n_ranks, msim_stats *out_stats, msim_sums *opt_sums,
                                msim_order_stat *out_order);
+
+/* Tail statistics: the moments of a column over the runs that lie below, or at, a quantile of a column. (No
+ * reference counterpart: the reference prints three means per miner, main.cpp:224-234.) An order statistic says
+ * what a bad year looks like as one number; these sums say how bad those years are on average (the expected
+ * shortfall), what else happened in them (the same miner's stale rate, every other miner's share), and what the same
+ * seeds gave at another point of a sweep. Quantities are indexed as for msim_order_stat: 0 = found, 1 = stale,
+ * 2 = share_t, 3 = rate_t; and keys are the uint64 terms of msim_moments.
+ * For run r of an item, `key` is the quantity's term of record (cond_point, r, cond_column) with that point's best
+ * height. The run belongs to `below` if key < value, to `equal` if key == value, and to neither otherwise. For each
+ * set the target column's record (target_point, r, target_column) contributes exactly what it contributes to its
+ * msim_moments, with the target point's own best height. The condition and the target may lie at different points
+ * of a sweep: a sweep runs every point on the same seeds, so run r is the same draws on both sides.
+ * Everything is a plain integer sum in msim_moments' limb convention: identical for any split into workgroups,
+ * chunks, launches or ranks, and it can be all-reduced. Unnormalised limbs of a subset never exceed the same limbs
+ * over all runs, so the complement sets follow by limb-wise subtraction from the target column's total
+ * msim_moments, with nothing recomputed: above = total - below - equal, at least = total - below.
+ * `value` is usually the value of an msim_order_stat; then n_below and n_equal reproduce its `below` and `equal`
+ * (two independent kernels). Any other threshold is allowed: quantity 0 with value 1 makes `below` the runs without
+ * a single block.
+ * Ties. The k smallest runs of a column (k = r + 1 for a 0-based rank r, so n_below < k <= n_below + n_equal) are all
+ * of `below` plus k - n_below of the ties; which ties is not a property of the data. Every tie is weighted by
+ * (k - n_below) / n_equal, the expectation over a uniformly random choice among the ties: deterministic, and
+ * independent of any split of the runs. For a first sum S of the target column:
+ *   mean_k = (S_below * n_equal + (k - n_below) * S_equal) / (k * n_equal)
+ * numerator and denominator formed exactly, then one correctly rounded f64 division. Where the target is the
+ * condition's own column and quantity, S_equal = n_equal * value and mean_k is exactly the expected shortfall
+ * (S_below + (k - n_below) value) / k. The upper form, the k largest, mirrors it on `above` and `equal`. */
+typedef struct msim_tail_item {      /* 32 bytes */
+    uint32_t cond_point, cond_column, quantity; /* the column and quantity whose key is compared */
+    uint32_t target_point, target_column;       /* the column whose moments are summed */
+    uint32_t reserved;                          /* 0 */
+    uint64_t value;                             /* the threshold */
+} msim_tail_item;
+typedef struct msim_tail {           /* 42 uint64 */
+    uint64_t n_below, n_equal;       /* #{runs: key < value}, #{runs: key == value} */
+    msim_moments below, equal;       /* msim_moments of the TARGET column over those two sets of runs */
+} msim_tail;
+#define MSIM_MAX_TAIL_ITEMS 8388480u /* 65 535 tiles of 128 items: the grid of one msim_tail_launch */
+
+/* Device-resident and asynchronous on `stream`, as msim_cross_launch: no allocation, no synchronisation,
+ * independent of any config, capturable. d_per_run / d_best_height: as msim_moments_launch. d_items: n_items
+ * msim_tail_item in device memory, 16-byte aligned. d_tails: n_items msim_tail, overwritten (zeroed inside the
+ * launch). An item with a point >= n_points, a column >= m, a quantity >= 4 or reserved != 0 reads nothing and leaves
+ * its 42 words zero (the launch cannot see device memory; validate on the host with msim_tail_items_check).
+ * MSIM_E_INVALID, with nothing written, for m == 0, no points, no runs, more than 2^32 - 1 runs per point,
+ * n_items == 0 or above MSIM_MAX_TAIL_ITEMS, or a null pointer. Item lists are best column-minor (consecutive items
+ * on consecutive columns), so that consecutive lanes read consecutive records.
+ * A test switch, MSIM_TAIL_TEST_WG_RUNS=<n> (n > 0), read at every launch: it only lowers the number of runs a
+ * workgroup takes (the smaller of the natural value and n), so a few hundred runs give several workgroups along
+ * the run axis. */
+int msim_tail_launch(uint32_t m, uint32_t n_points, uint64_t runs_per_point, const void *d_per_run,
+                     const void *d_best_height, const void *d_items, uint32_t n_items, void *d_tails, void *stream);
+/* Host only: MSIM_OK when there are 1..MSIM_MAX_TAIL_ITEMS items and every one lies within n_points x m with a
+ * quantity below 4 and reserved == 0, else MSIM_E_INVALID. */
+int msim_tail_items_check(uint32_t m, uint32_t n_points, const msim_tail_item *items, uint32_t n_items);
+
+/* Host only: the chosen set's msim_moments and run count. ABOVE and AT_LEAST need the target column's total moments
+ * over the n_runs runs (total_or_NULL); the other two ignore it. MSIM_E_INVALID for a null pointer, an unknown side,
+ * counts that exceed n_runs, or a total that some limb of the tail exceeds. `out` is a plain msim_moments, so
+ * msim_moments_to_errors(out, 1, *out_n, ...) gives the conditional means with standard errors unchanged. That error
+ * is the one of a sample of *out_n runs GIVEN the threshold: it does not include the sampling error of the threshold
+ * itself (of the quantile that chose the runs). */
+enum { MSIM_TAIL_BELOW, MSIM_TAIL_AT_MOST, MSIM_TAIL_ABOVE, MSIM_TAIL_AT_LEAST };
+int msim_tail_side(const msim_tail *t, const msim_moments *total_or_NULL, uint64_t n_runs, int side,
+                   msim_moments *out, uint64_t *out_n);
+/* Host only: mean_k of found, stale, share (x 2^-32) and rate (x 2^-32) of the target over the k smallest (upper = 0)
+ * or k largest (upper = 1, needs the total) runs of the condition, ties weighted as above. MSIM_E_INVALID unless k
+ * lies in the tie range (n_strict < k <= n_strict + n_equal, n_strict = n_below or the count above). */
+int msim_tail_means(const msim_tail *t, const msim_moments *total_or_NULL, uint64_t n_runs, uint64_t k, int upper,
+                    double out[4]);
+
+/* msim_run_order_stats / msim_sweep_run_order_stats plus the tails at the selected order statistics. A spec names a
+ * condition (point, column, quantity), which of the `ranks` supplies the threshold (rank_index < n_ranks) and a
+ * target (point, column); columns are classes with a class map, as for out_order. The runs are simulated once in
+ * chunks whose (folded) records stay resident; every chunk also runs msim_moments_launch, and the chunks' totals are
+ * added limb by limb on the host (out_moments: n_points * columns entries). After the eight selection passes the
+ * order statistics come to the host, every spec becomes an item whose value is its order statistic's, the items are
+ * uploaded once and msim_tail_launch runs on every resident buffer; the chunks' words are added on the host
+ * (out_tails: n_specs entries, whose n_below / n_equal equal the order statistic's below / equal). Everything
+ * msim_run_order_stats validates is validated, and the specs against (n_points, columns, n_ranks), 1..
+ * MSIM_MAX_TAIL_ITEMS of them; MSIM_E_CAPACITY on a failed run. They follow MSIM_MOMENTS_CHUNK_RUNS. */
+typedef struct msim_tail_spec {
+    uint32_t cond_point, cond_column, quantity, rank_index, target_point, target_column;
+} msim_tail_spec;
+int msim_run_tails(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                   const uint32_t *class_of_or_NULL, uint32_t n_classes, const uint64_t *ranks, uint32_t n_ranks,
+                   const msim_tail_spec *specs, uint32_t n_specs, msim_stats *out_stats, msim_sums *opt_sums,
+                   msim_order_stat *out_order, msim_moments *out_moments, msim_tail *out_tails);
+int msim_sweep_run_tails(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base,
+                         int device, const uint32_t *class_of_or_NULL, uint32_t n_classes, const uint64_t *ranks,
+                         uint32_t n_ranks, const msim_tail_spec *specs, uint32_t n_specs, msim_stats *out_stats,
+                         msim_sums *opt_sums, msim_order_stat *out_order, msim_moments *out_moments,
+                         msim_tail *out_tails);
 
 /* Convert fixed-point sums to MinerStats-style doubles. */
 void msim_sums_to_stats(const msim_sums *sums, uint32_t n, msim_stats *out);

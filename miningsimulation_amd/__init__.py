@@ -67,6 +67,17 @@ from .quantiles import (  # noqa: F401,E402
     report_quantiles,
 )
 
+from .tails import (  # noqa: F401,E402
+    TailItem,
+    TailResult,
+    TailSpec,
+    items_words,
+    own_tails,
+    report_tails,
+    tails_from_words,
+    tails_given,
+)
+
 from . import model  # noqa: F401,E402  (first-order analytical stale-rate model, plot.py restated)
 
 __version__ = "0.1.0"

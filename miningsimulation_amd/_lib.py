@@ -84,10 +84,18 @@ EXPORTED = (
     "msim_ranks_check",
     "msim_run_order_stats",
     "msim_sweep_run_order_stats",
+    "msim_tail_launch",
+    "msim_tail_items_check",
+    "msim_tail_side",
+    "msim_tail_means",
+    "msim_run_tails",
+    "msim_sweep_run_tails",
 )
 MSIM_CLASS_NONE = 0xFFFFFFFF
 MSIM_MAX_RANKS = 32
 MSIM_RANK_PASSES = 8
+MSIM_MAX_TAIL_ITEMS = 65535 * 128
+MSIM_TAIL_BELOW, MSIM_TAIL_AT_MOST, MSIM_TAIL_ABOVE, MSIM_TAIL_AT_LEAST = range(4)
 
 
 class MsimTiming(ctypes.Structure):
@@ -199,6 +207,23 @@ class MsimContrast(ctypes.Structure):
 class MsimOrderStat(ctypes.Structure):
     """msim_order_stat: the r-th smallest key of a column, and how many keys lie below it and equal it."""
     _fields_ = [("value", ctypes.c_uint64), ("below", ctypes.c_uint64), ("equal", ctypes.c_uint64)]
+
+
+class MsimTailItem(ctypes.Structure):
+    """msim_tail_item: the condition (point, column, quantity), the target (point, column) and the threshold."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("cond_point", "cond_column", "quantity", "target_point",
+                                               "target_column", "reserved")] + [("value", ctypes.c_uint64)]
+
+
+class MsimTail(ctypes.Structure):
+    """msim_tail: 42 uint64 per item, the run counts below and at the threshold and the target's moments over them."""
+    _fields_ = [("n_below", ctypes.c_uint64), ("n_equal", ctypes.c_uint64), ("below", MsimMoments),
+                ("equal", MsimMoments)]
+
+
+class MsimTailSpec(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("cond_point", "cond_column", "quantity", "rank_index", "target_point",
+                                               "target_column")]
 
 
 def _load() -> ctypes.CDLL:
@@ -341,6 +366,23 @@ def _load() -> ctypes.CDLL:
     lib.msim_run_order_stats.restype = ctypes.c_int
     lib.msim_sweep_run_order_stats.argtypes = lib.msim_run_order_stats.argtypes
     lib.msim_sweep_run_order_stats.restype = ctypes.c_int
+    lib.msim_tail_launch.argtypes = [u32, u32, u64, vp, vp, vp, u32, vp, vp]
+    lib.msim_tail_launch.restype = ctypes.c_int
+    lib.msim_tail_items_check.argtypes = [u32, u32, ctypes.POINTER(MsimTailItem), u32]
+    lib.msim_tail_items_check.restype = ctypes.c_int
+    lib.msim_tail_side.argtypes = [ctypes.POINTER(MsimTail), ctypes.POINTER(MsimMoments), u64, ctypes.c_int,
+                                   ctypes.POINTER(MsimMoments), ctypes.POINTER(u64)]
+    lib.msim_tail_side.restype = ctypes.c_int
+    lib.msim_tail_means.argtypes = [ctypes.POINTER(MsimTail), ctypes.POINTER(MsimMoments), u64, u64, ctypes.c_int,
+                                    ctypes.POINTER(ctypes.c_double)]
+    lib.msim_tail_means.restype = ctypes.c_int
+    lib.msim_run_tails.argtypes = [vp, u64, u64, u32, ctypes.c_int, ctypes.POINTER(u32), u32, ctypes.POINTER(u64), u32,
+                                   ctypes.POINTER(MsimTailSpec), u32, ctypes.POINTER(MsimStats),
+                                   ctypes.POINTER(MsimSums), ctypes.POINTER(MsimOrderStat),
+                                   ctypes.POINTER(MsimMoments), ctypes.POINTER(MsimTail)]
+    lib.msim_run_tails.restype = ctypes.c_int
+    lib.msim_sweep_run_tails.argtypes = lib.msim_run_tails.argtypes
+    lib.msim_sweep_run_tails.restype = ctypes.c_int
     lib.msim_version.argtypes = []
     lib.msim_version.restype = ctypes.c_char_p
     return lib

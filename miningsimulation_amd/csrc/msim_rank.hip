@@ -29,6 +29,7 @@
 
 #include "msim_host.h"
 #include "msim_rank.h"
+#include "msim_tail.h"
 
 namespace msim {
 
@@ -365,19 +366,42 @@ struct Resident {
     uint64_t runs;
 };
 
+// What msim_run_tails adds to the order statistics' job (null for the order statistics alone): the columns' total
+// moments, summed per chunk, and the tails at the selected order statistics, summed per resident buffer.
+struct TailJob {
+    const msim_tail_spec *specs;
+    uint32_t n_specs;
+    msim_moments *out_moments;  // [np][columns]
+    msim_tail *out_tails;       // [n_specs]
+};
+
 // Runs [run_begin, run_begin + runs) of n_points networks of m miners in chunks, each launched once into a record
 // buffer that stays resident (with a class map: launched into one per-miner buffer and folded into the chunk's own);
-// then begin, and per pass one count launch per chunk and one step.
+// then begin, and per pass one count launch per chunk and one step. With a TailJob every chunk also runs
+// msim_moments_launch, and after the last step the specs become items (value = the spec's order statistic) and
+// msim_tail_launch runs on every resident buffer.
 template <class WsBytes, class Launch>
 int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, int device, const uint32_t *class_of,
                    uint32_t n_classes, const uint64_t *ranks, uint32_t n_ranks, msim_stats *out_stats,
-                   msim_sums *opt_sums, msim_order_stat *out_order, bool general, WsBytes ws_bytes, Launch launch)
+                   msim_sums *opt_sums, msim_order_stat *out_order, bool general, WsBytes ws_bytes, Launch launch,
+                   const TailJob *tail = nullptr)
 {
     if (!out_stats || !out_order || runs == 0 || m == 0 || np == 0 || np > 65535) return MSIM_E_INVALID;
     if ((class_of == nullptr) != (n_classes == 0)) return MSIM_E_INVALID;
     if (class_of && msim_classes_check(m, class_of, n_classes) != MSIM_OK) return MSIM_E_INVALID;
     if (msim_ranks_check(runs, ranks, n_ranks) != MSIM_OK) return MSIM_E_INVALID;
     const uint32_t mc = class_of ? n_classes : m;  // columns of the selection
+    if (tail) {
+        if (!tail->specs || !tail->out_moments || !tail->out_tails || tail->n_specs == 0 ||
+            tail->n_specs > MSIM_MAX_TAIL_ITEMS)
+            return MSIM_E_INVALID;
+        for (uint32_t i = 0; i < tail->n_specs; ++i) {
+            const msim_tail_spec &sp = tail->specs[i];
+            if (sp.cond_point >= np || sp.target_point >= np || sp.cond_column >= mc || sp.target_column >= mc ||
+                sp.quantity >= msim::RANK_QUANTITIES || sp.rank_index >= n_ranks)
+                return MSIM_E_INVALID;
+        }
+    }
     if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
     uint64_t chunk = msim::MAX_LAUNCH_RUNS / np;
     const uint64_t by_bytes = RANK_CHUNK_BYTES / ((uint64_t)np * m * sizeof(msim_run_record));
@@ -392,14 +416,19 @@ int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, i
     if (!rwsb) return MSIM_E_INVALID;
     const size_t n_sums = 6 * (size_t)np * m, n_out = (size_t)np * mc * msim::RANK_QUANTITIES * n_ranks;
     std::vector<uint64_t> acc_s(n_sums, 0), part_s(n_sums);
+    const size_t n_mom = tail ? (size_t)np * mc * msim::MOM_WORDS : 0;
+    const size_t n_tw = tail ? (size_t)tail->n_specs * msim::TAIL_WORDS : 0;
+    std::vector<uint64_t> acc_m(n_mom, 0), part_m(n_mom), acc_t(n_tw, 0), part_t(n_tw);
     uint32_t st[2] = {0, 0}, bad = 0;
     if (general && !msim::workspace_fits(wsb)) return MSIM_E_MINERS;
-    msim::DevBuf ws, sums, status, rec, map, rws, order, rstatus;
+    msim::DevBuf ws, sums, status, rec, map, rws, order, rstatus, mom, items, tails;
     std::vector<Resident> kept((runs + chunk - 1) / chunk);
     msim::DevStream stream;  // after the buffers: destroyed before they are freed
     if (!ws.alloc(wsb) || !sums.alloc(n_sums * sizeof(uint64_t)) || !status.alloc(sizeof(st)) ||
         (class_of && (!map.alloc(m * sizeof(uint32_t)) || !rec.alloc(chunk * np * m * sizeof(msim_run_record)))) ||
         !rws.alloc(rwsb) || !order.alloc(n_out * sizeof(msim_order_stat)) || !rstatus.alloc(sizeof(uint32_t)) ||
+        (tail && (!mom.alloc(n_mom * sizeof(uint64_t)) || !items.alloc(tail->n_specs * sizeof(msim_tail_item)) ||
+                  !tails.alloc(n_tw * sizeof(uint64_t)))) ||
         !stream.create())
         return MSIM_E_HIP;
     hipStream_t s = stream.get();
@@ -419,12 +448,19 @@ int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, i
             rc = msim_fold_launch(m, np, cn, rec.get(), map.get(), mc, k.rec.get(), s);
             if (rc) return rc;
         }
+        if (tail) {
+            rc = msim_moments_launch(mc, np, cn, k.rec.get(), k.bh.get(), nullptr, mom.get(), nullptr, s);
+            if (rc) return rc;
+            if (hipMemcpyAsync(part_m.data(), mom.get(), n_mom * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess)
+                return MSIM_E_HIP;
+        }
         if (hipMemcpyAsync(part_s.data(), sums.get(), n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipMemcpyAsync(st, status.get(), sizeof(st), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return MSIM_E_HIP;
         if (st[1] != 0) return MSIM_E_CAPACITY;
         for (size_t i = 0; i < n_sums; ++i) acc_s[i] += part_s[i];
+        for (size_t i = 0; i < n_mom; ++i) acc_m[i] += part_m[i];
     }
     if (hipMemsetAsync(rstatus.get(), 0, sizeof(uint32_t), s) != hipSuccess) return MSIM_E_HIP;
     int rc = msim_rank_begin_launch(mc, np, ranks, n_ranks, rws.get(), rwsb, s);
@@ -440,6 +476,28 @@ int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, i
         hipStreamSynchronize(s) != hipSuccess)
         return MSIM_E_HIP;
     if (bad) return MSIM_E_INVALID;  // unreachable after msim_ranks_check
+    if (tail) {
+        std::vector<msim_tail_item> its(tail->n_specs);
+        for (uint32_t i = 0; i < tail->n_specs; ++i) {
+            const msim_tail_spec &sp = tail->specs[i];
+            const size_t at_o = (((size_t)sp.cond_point * mc + sp.cond_column) * msim::RANK_QUANTITIES + sp.quantity) * n_ranks;
+            its[i] = msim_tail_item{sp.cond_point, sp.cond_column, sp.quantity, sp.target_point, sp.target_column, 0,
+                                    got[at_o + sp.rank_index].value};
+        }
+        if (hipMemcpyAsync(items.get(), its.data(), its.size() * sizeof(msim_tail_item), hipMemcpyHostToDevice, s) != hipSuccess)
+            return MSIM_E_HIP;
+        for (size_t i = 0; i < kept.size(); ++i) {
+            rc = msim_tail_launch(mc, np, kept[i].runs, kept[i].rec.get(), kept[i].bh.get(), items.get(), tail->n_specs,
+                                  tails.get(), s);
+            if (rc) return rc;
+            if (hipMemcpyAsync(part_t.data(), tails.get(), n_tw * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess)
+                return MSIM_E_HIP;
+            for (size_t j = 0; j < n_tw; ++j) acc_t[j] += part_t[j];
+        }
+        memcpy(tail->out_moments, acc_m.data(), n_mom * sizeof(uint64_t));
+        memcpy(tail->out_tails, acc_t.data(), n_tw * sizeof(uint64_t));
+    }
     if (opt_sums) memcpy(opt_sums, acc_s.data(), n_sums * sizeof(uint64_t));
     msim_sums_to_stats((const msim_sums *)acc_s.data(), np * m, out_stats);
     memcpy(out_order, got.data(), n_out * sizeof(msim_order_stat));
@@ -478,6 +536,42 @@ int msim_sweep_run_order_stats(const msim_sweep *sweep, uint64_t run_begin, uint
         [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
             return msim_sweep_launch(sweep, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
         });
+}
+
+int msim_run_tails(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                   const uint32_t *class_of_or_NULL, uint32_t n_classes, const uint64_t *ranks, uint32_t n_ranks,
+                   const msim_tail_spec *specs, uint32_t n_specs, msim_stats *out_stats, msim_sums *opt_sums,
+                   msim_order_stat *out_order, msim_moments *out_moments, msim_tail *out_tails)
+{
+    if (!cfg) return MSIM_E_INVALID;
+    msim_pipeline_layout pl;
+    const bool general = msim_pipeline_info(cfg, 1, &pl) == MSIM_OK && pl.uses_pipeline == 4;
+    const TailJob job = {specs, n_specs, out_moments, out_tails};
+    return run_order_impl(
+        msim_config_miner_count(cfg), 1, run_begin, n_runs, device, class_of_or_NULL, n_classes, ranks, n_ranks,
+        out_stats, opt_sums, out_order, general, [&](uint64_t n) { return msim_workspace_bytes(cfg, n); },
+        [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
+            return msim_launch(cfg, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
+        },
+        &job);
+}
+
+int msim_sweep_run_tails(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base,
+                         int device, const uint32_t *class_of_or_NULL, uint32_t n_classes, const uint64_t *ranks,
+                         uint32_t n_ranks, const msim_tail_spec *specs, uint32_t n_specs, msim_stats *out_stats,
+                         msim_sums *opt_sums, msim_order_stat *out_order, msim_moments *out_moments,
+                         msim_tail *out_tails)
+{
+    if (!sweep) return MSIM_E_INVALID;
+    const TailJob job = {specs, n_specs, out_moments, out_tails};
+    return run_order_impl(
+        msim_sweep_miner_count(sweep), msim_sweep_point_count(sweep), run_begin, runs_per_point, device,
+        class_of_or_NULL, n_classes, ranks, n_ranks, out_stats, opt_sums, out_order, false,
+        [&](uint64_t n) { return msim_sweep_workspace_bytes(sweep, n); },
+        [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
+            return msim_sweep_launch(sweep, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
+        },
+        &job);
 }
 
 }  // extern "C"

@@ -349,3 +349,112 @@ def run_sharded_quantiles(sim, n_total: int, seed_base: int, qs=(0.05, 0.5, 0.95
     )
     return QuantileResult(points=[res], ranks=sel, qs=None if ranks is not None else [float(q) for q in qs],
                           order=order_stats_from_words(out.cpu().numpy(), 1, m, len(sel)), n_runs=n_total)
+
+
+def run_sharded_tails(sim, n_total: int, seed_base: int, q=0.05, ranks=None, specs=None, run_begin: int = 0,
+                      stream=None, launch: Optional[Callable] = None, launch_rank_begin: Optional[Callable] = None,
+                      launch_rank_count: Optional[Callable] = None, launch_rank_step: Optional[Callable] = None,
+                      launch_moments: Optional[Callable] = None, launch_tails: Optional[Callable] = None,
+                      device=None, max_chunk: int = MAX_LAUNCH_RUNS):
+    """run_sharded_quantiles plus the tail statistics at the selected order statistics (tails.py) over ALL n_total
+    runs. Two things are added to that job. Every chunk also runs msim_moments_launch, and the columns' total moments
+    ride behind the sums and status words in the first pass's all-reduce. After the last step every rank holds the
+    same order statistics, builds the same items from `specs` (tails.own_tails by default), runs msim_tail_launch on
+    each of its resident buffers and adds the words; ONE more all-reduce of the tails' words follows: nine
+    all-reduces per job. Everything reduced is an integer sum over runs, so the result is identical on every rank
+    and for every world size.
+
+    Returns a TailResult. The `launch*` callables replace sim.launch, sim.launch_rank_*, sim.launch_moments and
+    sim.launch_tails (same signatures, workspace None for the launch) so that CPU ranks with a gloo group can
+    exercise the job."""
+    import contextlib
+
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    from ._lib import MsimSums
+    from .moments import MOMENT_WORDS
+    from .quantiles import (RANK_PASSES, order_stats_from_words, quantile_rank, rank_counts_view, rank_workspace_bytes,
+                            ranks_array)
+    from .simulation import SimulationResult, sums_to_stats
+    from .tails import TAIL_WORDS, _q_list, items_from_specs, items_words, make_result, own_tails, specs_struct
+
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    begin, n = shard(n_total, world, rank)
+    m = len(sim.miners)
+    qs = None if ranks is not None else _q_list(q)
+    sel = [int(r) for r in ranks] if ranks is not None else [quantile_rank(n_total, x) for x in qs]
+    ranks_array(sel, n_total)  # ValueError for a rank that is not below n_total
+    specs, _ = specs_struct(own_tails(1, m) if specs is None else specs, 1, m, len(sel))
+    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    ws_words = rank_workspace_bytes(m, 1, len(sel)) // 8
+    c_off, c_words = rank_counts_view(m, 1, len(sel))
+    assert c_off % 8 == 0 and c_off // 8 + c_words == ws_words  # the counts end the workspace
+    # the workspace with the sums, the two status words and the total moments behind its counts: they join the first
+    # all-reduce
+    o_status, o_mom = ws_words + 6 * m, ws_words + 6 * m + 2
+    buf = torch.zeros(o_mom + MOMENT_WORDS * m, dtype=torch.int64, device=dev)
+    d_ws = buf[:ws_words]
+    sums = buf[ws_words:o_status].view(m, 6)
+    status = buf[o_status:o_mom]
+    moments = buf[o_mom:].view(m, MOMENT_WORDS)
+    part = torch.zeros((m, 6), dtype=torch.int64, device=dev)
+    pst = torch.zeros(2, dtype=torch.int32, device=dev)
+    pmom = torch.zeros((m, MOMENT_WORDS), dtype=torch.int64, device=dev)
+    out = torch.zeros((m, 4, len(sel), 3), dtype=torch.int64, device=dev)
+    rst = torch.zeros(1, dtype=torch.int32, device=dev)
+    tails = torch.zeros((len(specs), TAIL_WORDS), dtype=torch.int64, device=dev)
+    ptail = torch.zeros((len(specs), TAIL_WORDS), dtype=torch.int64, device=dev)
+    chunk = min(n, max_chunk)
+    ws = None
+    if n and launch is None:
+        ws = torch.empty(sim.workspace_bytes(chunk), dtype=torch.uint8, device=dev)
+    kept = []
+    ctx = torch.cuda.stream(stream) if (stream is not None and dev.type == "cuda") else contextlib.nullcontext()
+    if stream is not None and dev.type == "cuda":
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    with ctx:
+        for off in range(0, n, max(chunk, 1)):
+            cn = min(chunk, n - off)
+            rec = torch.zeros((cn, m, 2), dtype=torch.int32, device=dev)
+            bh = torch.zeros(cn, dtype=torch.int32, device=dev)
+            (launch or sim.launch)(cn, run_begin + begin + off, seed_base, part, ws, pst, d_per_run=rec,
+                                   d_best_height=bh, stream=stream)
+            (launch_moments or sim.launch_moments)(cn, rec, bh, pmom, None, None, stream=stream)
+            sums += part
+            status += pst
+            moments += pmom
+            kept.append((cn, rec, bh))
+        (launch_rank_begin or sim.launch_rank_begin)(sel, d_ws, stream=stream)
+        for p in range(RANK_PASSES):
+            for cn, rec, bh in kept:
+                (launch_rank_count or sim.launch_rank_count)(cn, rec, bh, p, d_ws, stream=stream)
+            if world > 1:
+                dist.all_reduce(buf[c_off // 8:] if p == 0 else buf[c_off // 8:ws_words])
+            (launch_rank_step or sim.launch_rank_step)(p, d_ws, out, rst, stream=stream)
+        # the order statistics are the same on every rank, and so are the items built from them
+        if int(rst.cpu()[0]) != 0:
+            raise RuntimeError("a rank was not below the run count")
+        order = order_stats_from_words(out.cpu().numpy(), 1, m, len(sel))
+        items = items_from_specs(specs, order)
+        d_items = torch.from_numpy(items_words(items).view(np.int32)).to(dev)
+        for cn, rec, bh in kept:
+            (launch_tails or sim.launch_tails)(cn, rec, bh, d_items, len(items), ptail, stream=stream)
+            tails += ptail
+        if world > 1:
+            dist.all_reduce(tails)
+    if stream is not None and dev.type == "cuda":
+        torch.cuda.current_stream(dev).wait_stream(stream)
+    host = buf[ws_words:].cpu()
+    if int(host[6 * m + 1]) != 0:
+        raise RuntimeError(f"{int(host[6 * m + 1])} runs exceeded the compact state capacity")
+    rows = host[:6 * m].view(m, 6).tolist()
+    u64 = (lambda v: int(v) & 0xFFFFFFFFFFFFFFFF)
+    res = SimulationResult(
+        stats_total=sums_to_stats([[u64(x) for x in r] for r in rows]),
+        sums=[MsimSums(r[0], r[1], u64(r[2]), u64(r[3]), u64(r[4]), u64(r[5])) for r in rows],
+        n_runs=n_total,
+    )
+    return make_result([res], sel, qs, order, n_total, specs, host[6 * m + 2:].numpy(), tails.cpu().numpy())

@@ -27,6 +27,7 @@ from .contrasts import CROSS_WORDS, Pair, cross_from_words, pairs_struct
 from .moments import MOMENT_WORDS, HistSpec, moments_from_words
 from .quantiles import (QuantileResult, _launch_rank_begin, _launch_rank_count, _launch_rank_step, _run_quantiles,
                         rank_counts_view, rank_workspace_bytes)
+from .tails import TailResult, TailSpec, _launch_tails, _run_tails
 
 SIM_DURATION_MS = 31_556_952_000  # main.cpp:7 std::chrono::months{12}
 SIM_RUNS = 16 * 2048              # main.cpp:10
@@ -383,6 +384,23 @@ class Simulation:
         may be None), d_status int32 [1] (added to)."""
         _launch_rank_step(columns or len(self.miners), 1, pass_, d_ws, d_out, d_status, stream)
 
+    def run_tails(self, n_runs: int, q=0.05, *, ranks: Optional[Sequence[int]] = None,
+                  specs: Optional[Sequence[TailSpec]] = None, class_of: Optional[Sequence[int]] = None,
+                  n_classes: Optional[int] = None, seed_base: int = DEFAULT_SEED_BASE, run_begin: int = 0,
+                  device: int = 0) -> TailResult:
+        """msim_run_tails: run_quantiles() at the quantile(s) `q` (or the 0-based `ranks`) plus the columns' total
+        moments and, per spec (tails.own_tails by default: every column's own share at rank index 0), the target
+        column's moments over the runs below and at the selected order statistic. result.means(i),
+        result.expected_shortfall(column), result.side(i, ...) and report_tails(miners, result) work on it."""
+        return _run_tails(lib.msim_run_tails, "msim_run_tails", self._h, 1, len(self.miners), n_runs, q, ranks, specs,
+                          class_of, n_classes, run_begin, seed_base, device)
+
+    def launch_tails(self, n_runs: int, d_per_run, d_best_height, d_items, n_items: int, d_tails, stream=None,
+                     columns: Optional[int] = None) -> None:
+        """msim_tail_launch on the current device over a launch's records: d_items int32 [n_items, 8]
+        (tails.items_words) and d_tails int64 [n_items, 42] (overwritten); the other buffers as launch_moments."""
+        _launch_tails(columns or len(self.miners), 1, n_runs, d_per_run, d_best_height, d_items, n_items, d_tails, stream)
+
     def run_multi(self, n_runs: int, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
                   devices: Sequence[int] = (0,)) -> SimulationResult:
         """msim_run_multi: the runs sharded over `devices` (one host thread each) and combined with one RCCL
@@ -603,6 +621,21 @@ class Sweep:
     def launch_rank_step(self, pass_: int, d_ws, d_out, d_status, stream=None, columns: Optional[int] = None) -> None:
         """msim_rank_step_launch; d_out int64 [n_points, M, 4, n_ranks, 3]."""
         _launch_rank_step(columns or self.m, len(self.sims), pass_, d_ws, d_out, d_status, stream)
+
+    def run_tails(self, runs_per_point: int, q=0.05, *, ranks: Optional[Sequence[int]] = None,
+                  specs: Optional[Sequence[TailSpec]] = None, class_of: Optional[Sequence[int]] = None,
+                  n_classes: Optional[int] = None, seed_base: int = DEFAULT_SEED_BASE, run_begin: int = 0,
+                  device: int = 0) -> TailResult:
+        """msim_sweep_run_tails: Simulation.run_tails over a sweep; a spec's condition and target may lie at
+        different points (the same seeds on both sides)."""
+        return _run_tails(lib.msim_sweep_run_tails, "msim_sweep_run_tails", self._h, len(self.sims), self.m,
+                          runs_per_point, q, ranks, specs, class_of, n_classes, run_begin, seed_base, device)
+
+    def launch_tails(self, runs_per_point: int, d_per_run, d_best_height, d_items, n_items: int, d_tails, stream=None,
+                     columns: Optional[int] = None) -> None:
+        """msim_tail_launch over a sweep launch's records."""
+        _launch_tails(columns or self.m, len(self.sims), runs_per_point, d_per_run, d_best_height, d_items, n_items,
+                      d_tails, stream)
 
     def workspace_bytes(self, runs_per_point: int) -> int:
         return int(lib.msim_sweep_workspace_bytes(self._h, runs_per_point))
