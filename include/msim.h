@@ -717,6 +717,97 @@ int msim_sweep_run_tails(const msim_sweep *sweep, uint64_t run_begin, uint64_t r
                          msim_sums *opt_sums, msim_order_stat *out_order, msim_moments *out_moments,
                          msim_tail *out_tails);
 
+/* Bootstrap: resampled quantiles and expected shortfalls with integer weights, exact on the device. (No reference
+ * counterpart.) A Poisson bootstrap gives run r the weight boot_weight(seed, b, r) in replicate b: 1 for b == 0 (the
+ * data itself), else with G = 0x9E3779B97F4A7C15 and mix = SplitMix64's output function
+ *   c = mix(seed ^ ((uint64)(b >> 1) * G)),  z = mix(c + G * (r + 1)),  u = b odd ? z >> 32 : z & 0xFFFFFFFF,
+ *   weight = #{k in 0..12 : u >= T[k]},  T[k] = floor(2^32 * sum_{i<=k} e^-1 / i!)   (csrc/msim_boot.h),
+ * Poisson(1) to within 2^-32 per cell and at most 13. r is the ABSOLUTE run index; nothing else enters the weight
+ * (not the point, column, chunk, shard or workgroup), so replicates are paired across the points of a sweep and
+ * identical for any split of the runs. W_b = sum_r weight is the replicate's size (W_0 = N) and its rank is
+ * max(1, ceil(q W_b)) - 1 with q W_b the rounded double product. An item names (point, column, quantity, q_index);
+ * per (item, replicate) the row is the order statistic at that rank of the weighted multiset of keys and the
+ * weighted sum of the keys below it, in two halves:
+ *   below = sum w [key < value],  equal = sum w [key == value],
+ *   s_hi = sum w (key >> 32) [key < value],  s_lo = sum w (key & 0xFFFFFFFF) [key < value].
+ * The replicate's expected shortfall is (S_below + (k - below) value) / k with k = rank + 1 and
+ * S_below = s_hi 2^32 + s_lo (msim_tail's tie convention). A replicate with W_b == 0 has no quantile: its rows are
+ * all zero, and equal == 0 marks them. s_hi is exact while 13 * 2^32 * N < 2^64: the drivers refuse
+ * N >= MSIM_BOOT_MAX_RUNS runs per point. The selection is msim_rank's, eight passes of weighted digit counts, all
+ * plain integer sums: identical for any split and world size, and they can be all-reduced. */
+#define MSIM_MAX_BOOT_REPLICATES 4096u /* rows of one item; the ranks of one quantile */
+#define MSIM_MAX_BOOT_ITEMS 65535u     /* the grid's z extent of a count launch */
+#define MSIM_BOOT_MAX_RUNS (1ull << 28)
+#define MSIM_BOOT_EMPTY 0xFFFFFFFFFFFFFFFFull /* the rank that marks an empty replicate in `ranks` */
+typedef struct msim_boot_item {
+    uint32_t point, column, quantity, q_index;
+} msim_boot_item;
+typedef struct msim_boot_row {
+    uint64_t value, below, equal, s_hi, s_lo;
+} msim_boot_row; /* per [item][replicate] */
+
+/* Host only: bytes of workspace for n_items items of B replicates (header, items, three state words per row and
+ * n_items * B * 256 uint64 counts); 0 for n_items outside 1..MSIM_MAX_BOOT_ITEMS or B outside
+ * 1..MSIM_MAX_BOOT_REPLICATES. msim_boot_counts_view: where the counts lie, as msim_rank_counts_view. */
+size_t msim_boot_workspace_bytes(uint32_t n_items, uint32_t replicates);
+int msim_boot_counts_view(uint32_t n_items, uint32_t replicates, size_t *offset, size_t *words);
+/* Host only: MSIM_OK for 1..MSIM_MAX_BOOT_ITEMS items that all lie within n_points x m, with a quantity below 4 and
+ * q_index < n_q (n_q in 1..MSIM_MAX_RANKS), else MSIM_E_INVALID. */
+int msim_boot_items_check(uint32_t m, uint32_t n_points, uint32_t n_q, const msim_boot_item *items, uint32_t n_items);
+/* Host only: the rank of the q-quantile of a replicate of total weight W: max(1, ceil(q W)) - 1, or MSIM_BOOT_EMPTY
+ * for W == 0. q outside [0, 1] (or NaN) also gives MSIM_BOOT_EMPTY. */
+uint64_t msim_boot_rank(uint64_t total_weight, double q);
+/* The launches are device-resident and asynchronous on `stream` unless said otherwise; all return MSIM_E_INVALID,
+ * with nothing written, for a zero count, a count past its cap, more than 2^32 - 1 runs per point, more than
+ * 65 535 points, pass >= MSIM_RANK_PASSES, a workspace that is too small, or a null pointer.
+ * weights: ADDS the weights of the absolute runs [run_begin, run_begin + runs) to d_W[replicates] (uint64; clear it
+ * before the first chunk). It serves chunks and shards: W is a plain sum. */
+int msim_boot_weights_launch(uint64_t seed, uint64_t run_begin, uint64_t runs, uint32_t replicates, void *d_W,
+                             void *stream);
+/* begin: `items` (checked with msim_boot_items_check) and ranks[n_q][replicates] are HOST memory, the ranks computed
+ * with msim_boot_rank from the complete W. Copies them into the workspace (which may hold anything before), sets every
+ * row to {prefix 0, remaining = its rank}, clears the counts and writes the header; the copy from host memory
+ * synchronises the stream once. A rank of MSIM_BOOT_EMPTY makes an empty row. */
+int msim_boot_begin_launch(uint32_t m, uint32_t n_points, const msim_boot_item *items, uint32_t n_items,
+                           uint32_t replicates, const uint64_t *ranks, uint32_t n_q, void *d_ws, size_t ws_bytes,
+                           void *stream);
+/* count, pass p: adds to every non-empty row's 256 counts the weights of the keys of [run_begin, run_begin + runs)
+ * that carry the row's prefix; never clears them, so several buffers (and an all-reduce) feed one pass. seed and
+ * run_begin (the absolute index of the buffer's first run) must be the ones of the weights launches. A workspace
+ * that begin did not prepare for the same m, n_points, n_items and replicates makes the launch do nothing.
+ * A test switch, MSIM_BOOT_TEST_WG_RUNS=<n> (n > 0), read at every count and below launch, only lowers the number of
+ * runs a workgroup takes (at most 2^24, so 13 * 2^24 cannot wrap a 32-bit counter). */
+int msim_boot_count_launch(uint32_t m, uint32_t n_points, uint64_t seed, uint64_t run_begin, uint64_t runs_per_point,
+                           const void *d_per_run, const void *d_best_height, uint32_t n_items, uint32_t replicates,
+                           uint32_t pass, void *d_ws, size_t ws_bytes, void *stream);
+/* step, pass p: narrows every row and zeroes its counts. At the last pass d_out_or_NULL is required:
+ * n_items * replicates msim_boot_row, whose five words are all written ({value, below, equal, 0, 0}; zeros for an
+ * empty row). d_status: one uint32_t the launch adds to for a row whose counts do not reach its rank (a rank that
+ * was not computed from W). Does nothing on an unprepared workspace. */
+int msim_boot_step_launch(uint32_t n_items, uint32_t replicates, uint32_t pass, void *d_ws, size_t ws_bytes,
+                          void *d_out_or_NULL, void *d_status, void *stream);
+/* below, after the last step: ADDS to s_hi and s_lo of every non-empty row of d_rows (the step's output) the
+ * weighted halves of the buffer's keys below the row's value. Items are read from the workspace. */
+int msim_boot_below_launch(uint32_t m, uint32_t n_points, uint64_t seed, uint64_t run_begin, uint64_t runs_per_point,
+                           const void *d_per_run, const void *d_best_height, uint32_t n_items, uint32_t replicates,
+                           void *d_ws, size_t ws_bytes, void *d_rows, void *stream);
+/* msim_run_order_stats / msim_sweep_run_order_stats plus the bootstrap of `items` at the quantiles qs[n_q] (each in
+ * [0, 1]) with `replicates` replicates: the same resident chunks and class-map folding; W per chunk from the weights
+ * launch; then begin, eight rounds of count-per-buffer and step, and the below pass. `ranks` are the order
+ * statistics' as before (for replicate 0 to be compared with, pass the ranks of qs over n_runs). out_W:
+ * [replicates]; out_rows: [n_items][replicates]. MSIM_E_INVALID also for n_runs >= MSIM_BOOT_MAX_RUNS. */
+int msim_run_bootstrap(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                       const uint32_t *class_of_or_NULL, uint32_t n_classes, const uint64_t *ranks, uint32_t n_ranks,
+                       const msim_boot_item *items, uint32_t n_items, const double *qs, uint32_t n_q,
+                       uint32_t replicates, uint64_t boot_seed, msim_stats *out_stats, msim_sums *opt_sums,
+                       msim_order_stat *out_order, uint64_t *out_W, msim_boot_row *out_rows);
+int msim_sweep_run_bootstrap(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base,
+                             int device, const uint32_t *class_of_or_NULL, uint32_t n_classes, const uint64_t *ranks,
+                             uint32_t n_ranks, const msim_boot_item *items, uint32_t n_items, const double *qs,
+                             uint32_t n_q, uint32_t replicates, uint64_t boot_seed, msim_stats *out_stats,
+                             msim_sums *opt_sums, msim_order_stat *out_order, uint64_t *out_W,
+                             msim_boot_row *out_rows);
+
 /* Convert fixed-point sums to MinerStats-style doubles. */
 void msim_sums_to_stats(const msim_sums *sums, uint32_t n, msim_stats *out);
 

@@ -78,6 +78,16 @@ from .tails import (  # noqa: F401,E402
     tails_given,
 )
 
+from .bootstrap import (  # noqa: F401,E402
+    BootItem,
+    BootstrapResult,
+    across_points,
+    boot_ranks,
+    launch_boot_weights,
+    own_bootstrap,
+    report_bootstrap,
+)
+
 from . import model  # noqa: F401,E402  (first-order analytical stale-rate model, plot.py restated)
 
 __version__ = "0.1.0"

@@ -90,11 +90,26 @@ EXPORTED = (
     "msim_tail_means",
     "msim_run_tails",
     "msim_sweep_run_tails",
+    "msim_boot_workspace_bytes",
+    "msim_boot_counts_view",
+    "msim_boot_items_check",
+    "msim_boot_rank",
+    "msim_boot_weights_launch",
+    "msim_boot_begin_launch",
+    "msim_boot_count_launch",
+    "msim_boot_step_launch",
+    "msim_boot_below_launch",
+    "msim_run_bootstrap",
+    "msim_sweep_run_bootstrap",
 )
 MSIM_CLASS_NONE = 0xFFFFFFFF
 MSIM_MAX_RANKS = 32
 MSIM_RANK_PASSES = 8
 MSIM_MAX_TAIL_ITEMS = 65535 * 128
+MSIM_MAX_BOOT_REPLICATES = 4096
+MSIM_MAX_BOOT_ITEMS = 65535
+MSIM_BOOT_MAX_RUNS = 1 << 28
+MSIM_BOOT_EMPTY = 0xFFFFFFFFFFFFFFFF
 MSIM_TAIL_BELOW, MSIM_TAIL_AT_MOST, MSIM_TAIL_ABOVE, MSIM_TAIL_AT_LEAST = range(4)
 
 
@@ -224,6 +239,16 @@ class MsimTail(ctypes.Structure):
 class MsimTailSpec(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("cond_point", "cond_column", "quantity", "rank_index", "target_point",
                                                "target_column")]
+
+
+class MsimBootItem(ctypes.Structure):
+    """msim_boot_item: the (point, column, quantity) whose key is resampled and the index of its quantile."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("point", "column", "quantity", "q_index")]
+
+
+class MsimBootRow(ctypes.Structure):
+    """msim_boot_row: one replicate's order statistic and the weighted sum of the keys below it, in two halves."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("value", "below", "equal", "s_hi", "s_lo")]
 
 
 def _load() -> ctypes.CDLL:
@@ -383,6 +408,32 @@ def _load() -> ctypes.CDLL:
     lib.msim_run_tails.restype = ctypes.c_int
     lib.msim_sweep_run_tails.argtypes = lib.msim_run_tails.argtypes
     lib.msim_sweep_run_tails.restype = ctypes.c_int
+    lib.msim_boot_workspace_bytes.argtypes = [u32, u32]
+    lib.msim_boot_workspace_bytes.restype = sz
+    lib.msim_boot_counts_view.argtypes = [u32, u32, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    lib.msim_boot_counts_view.restype = ctypes.c_int
+    lib.msim_boot_items_check.argtypes = [u32, u32, u32, ctypes.POINTER(MsimBootItem), u32]
+    lib.msim_boot_items_check.restype = ctypes.c_int
+    lib.msim_boot_rank.argtypes = [u64, ctypes.c_double]
+    lib.msim_boot_rank.restype = u64
+    lib.msim_boot_weights_launch.argtypes = [u64, u64, u64, u32, vp, vp]
+    lib.msim_boot_weights_launch.restype = ctypes.c_int
+    lib.msim_boot_begin_launch.argtypes = [u32, u32, ctypes.POINTER(MsimBootItem), u32, u32, ctypes.POINTER(u64), u32,
+                                           vp, sz, vp]
+    lib.msim_boot_begin_launch.restype = ctypes.c_int
+    lib.msim_boot_count_launch.argtypes = [u32, u32, u64, u64, u64, vp, vp, u32, u32, u32, vp, sz, vp]
+    lib.msim_boot_count_launch.restype = ctypes.c_int
+    lib.msim_boot_step_launch.argtypes = [u32, u32, u32, vp, sz, vp, vp, vp]
+    lib.msim_boot_step_launch.restype = ctypes.c_int
+    lib.msim_boot_below_launch.argtypes = [u32, u32, u64, u64, u64, vp, vp, u32, u32, vp, sz, vp, vp]
+    lib.msim_boot_below_launch.restype = ctypes.c_int
+    lib.msim_run_bootstrap.argtypes = [vp, u64, u64, u32, ctypes.c_int, ctypes.POINTER(u32), u32, ctypes.POINTER(u64),
+                                       u32, ctypes.POINTER(MsimBootItem), u32, ctypes.POINTER(ctypes.c_double), u32,
+                                       u32, u64, ctypes.POINTER(MsimStats), ctypes.POINTER(MsimSums),
+                                       ctypes.POINTER(MsimOrderStat), ctypes.POINTER(u64), ctypes.POINTER(MsimBootRow)]
+    lib.msim_run_bootstrap.restype = ctypes.c_int
+    lib.msim_sweep_run_bootstrap.argtypes = lib.msim_run_bootstrap.argtypes
+    lib.msim_sweep_run_bootstrap.restype = ctypes.c_int
     lib.msim_version.argtypes = []
     lib.msim_version.restype = ctypes.c_char_p
     return lib

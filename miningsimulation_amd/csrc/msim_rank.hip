@@ -27,6 +27,7 @@
 #include <memory>
 #include <vector>
 
+#include "msim_boot.h"
 #include "msim_host.h"
 #include "msim_rank.h"
 #include "msim_tail.h"
@@ -364,6 +365,7 @@ uint64_t chunk_cap()
 struct Resident {
     msim::DevBuf rec, bh;  // one chunk's (folded) records and best heights
     uint64_t runs;
+    uint64_t begin;  // the absolute index of the chunk's first run
 };
 
 // What msim_run_tails adds to the order statistics' job (null for the order statistics alone): the columns' total
@@ -375,16 +377,64 @@ struct TailJob {
     msim_tail *out_tails;       // [n_specs]
 };
 
+// What msim_run_bootstrap adds (null otherwise): the replicates' total weights, summed per chunk, and after the order
+// statistics the bootstrap's own selection and below pass over every resident buffer.
+struct BootJob {
+    const msim_boot_item *items;
+    uint32_t n_items;
+    const double *qs;
+    uint32_t n_q, replicates;
+    uint64_t seed;
+    uint64_t *out_W;          // [replicates]
+    msim_boot_row *out_rows;  // [n_items][replicates]
+};
+
+// Begin, eight rounds of count-per-buffer and step, then the below pass, on the stream `s`; W has been summed.
+int run_boot_job(const BootJob &job, uint32_t mc, uint32_t np, const std::vector<Resident> &kept, msim::DevBuf &dW,
+                 hipStream_t s)
+{
+    const uint32_t B = job.replicates;
+    const size_t bwsb = msim_boot_workspace_bytes(job.n_items, B);
+    const size_t n_rows = (size_t)job.n_items * B;
+    msim::DevBuf bws, rows, bstatus;
+    if (!bwsb || !bws.alloc(bwsb) || !rows.alloc(n_rows * sizeof(msim_boot_row)) || !bstatus.alloc(sizeof(uint32_t)))
+        return MSIM_E_HIP;
+    std::vector<uint64_t> ranks((size_t)job.n_q * B);
+    if (hipMemcpyAsync(job.out_W, dW.get(), B * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemsetAsync(bstatus.get(), 0, sizeof(uint32_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return MSIM_E_HIP;
+    for (uint32_t j = 0; j < job.n_q; ++j)
+        for (uint32_t b = 0; b < B; ++b) ranks[(size_t)j * B + b] = msim_boot_rank(job.out_W[b], job.qs[j]);
+    int rc = msim_boot_begin_launch(mc, np, job.items, job.n_items, B, ranks.data(), job.n_q, bws.get(), bwsb, s);
+    for (uint32_t pass = 0; rc == MSIM_OK && pass < MSIM_RANK_PASSES; ++pass) {
+        for (size_t i = 0; rc == MSIM_OK && i < kept.size(); ++i)
+            rc = msim_boot_count_launch(mc, np, job.seed, kept[i].begin, kept[i].runs, kept[i].rec.get(), kept[i].bh.get(),
+                                        job.n_items, B, pass, bws.get(), bwsb, s);
+        if (rc == MSIM_OK) rc = msim_boot_step_launch(job.n_items, B, pass, bws.get(), bwsb, rows.get(), bstatus.get(), s);
+    }
+    for (size_t i = 0; rc == MSIM_OK && i < kept.size(); ++i)
+        rc = msim_boot_below_launch(mc, np, job.seed, kept[i].begin, kept[i].runs, kept[i].rec.get(), kept[i].bh.get(),
+                                    job.n_items, B, bws.get(), bwsb, rows.get(), s);
+    if (rc) return rc;
+    uint32_t bad = 0;
+    if (hipMemcpyAsync(job.out_rows, rows.get(), n_rows * sizeof(msim_boot_row), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(&bad, bstatus.get(), sizeof(bad), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return MSIM_E_HIP;
+    return bad ? MSIM_E_INVALID : MSIM_OK;  // unreachable: the ranks come from W
+}
+
 // Runs [run_begin, run_begin + runs) of n_points networks of m miners in chunks, each launched once into a record
 // buffer that stays resident (with a class map: launched into one per-miner buffer and folded into the chunk's own);
 // then begin, and per pass one count launch per chunk and one step. With a TailJob every chunk also runs
 // msim_moments_launch, and after the last step the specs become items (value = the spec's order statistic) and
-// msim_tail_launch runs on every resident buffer.
+// msim_tail_launch runs on every resident buffer. With a BootJob every chunk also adds its weights to W, and
+// run_boot_job follows the order statistics.
 template <class WsBytes, class Launch>
 int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, int device, const uint32_t *class_of,
                    uint32_t n_classes, const uint64_t *ranks, uint32_t n_ranks, msim_stats *out_stats,
                    msim_sums *opt_sums, msim_order_stat *out_order, bool general, WsBytes ws_bytes, Launch launch,
-                   const TailJob *tail = nullptr)
+                   const TailJob *tail = nullptr, const BootJob *boot = nullptr)
 {
     if (!out_stats || !out_order || runs == 0 || m == 0 || np == 0 || np > 65535) return MSIM_E_INVALID;
     if ((class_of == nullptr) != (n_classes == 0)) return MSIM_E_INVALID;
@@ -401,6 +451,14 @@ int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, i
                 sp.quantity >= msim::RANK_QUANTITIES || sp.rank_index >= n_ranks)
                 return MSIM_E_INVALID;
         }
+    }
+    if (boot) {
+        if (!boot->qs || !boot->out_W || !boot->out_rows || runs >= MSIM_BOOT_MAX_RUNS ||
+            boot->replicates == 0 || boot->replicates > MSIM_MAX_BOOT_REPLICATES ||
+            msim_boot_items_check(mc, np, boot->n_q, boot->items, boot->n_items) != MSIM_OK)
+            return MSIM_E_INVALID;
+        for (uint32_t j = 0; j < boot->n_q; ++j)
+            if (!(boot->qs[j] >= 0.0 && boot->qs[j] <= 1.0)) return MSIM_E_INVALID;
     }
     if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
     uint64_t chunk = msim::MAX_LAUNCH_RUNS / np;
@@ -421,7 +479,7 @@ int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, i
     std::vector<uint64_t> acc_m(n_mom, 0), part_m(n_mom), acc_t(n_tw, 0), part_t(n_tw);
     uint32_t st[2] = {0, 0}, bad = 0;
     if (general && !msim::workspace_fits(wsb)) return MSIM_E_MINERS;
-    msim::DevBuf ws, sums, status, rec, map, rws, order, rstatus, mom, items, tails;
+    msim::DevBuf ws, sums, status, rec, map, rws, order, rstatus, mom, items, tails, bootW;
     std::vector<Resident> kept((runs + chunk - 1) / chunk);
     msim::DevStream stream;  // after the buffers: destroyed before they are freed
     if (!ws.alloc(wsb) || !sums.alloc(n_sums * sizeof(uint64_t)) || !status.alloc(sizeof(st)) ||
@@ -429,9 +487,10 @@ int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, i
         !rws.alloc(rwsb) || !order.alloc(n_out * sizeof(msim_order_stat)) || !rstatus.alloc(sizeof(uint32_t)) ||
         (tail && (!mom.alloc(n_mom * sizeof(uint64_t)) || !items.alloc(tail->n_specs * sizeof(msim_tail_item)) ||
                   !tails.alloc(n_tw * sizeof(uint64_t)))) ||
-        !stream.create())
+        (boot && !bootW.alloc(boot->replicates * sizeof(uint64_t))) || !stream.create())
         return MSIM_E_HIP;
     hipStream_t s = stream.get();
+    if (boot && hipMemsetAsync(bootW.get(), 0, boot->replicates * sizeof(uint64_t), s) != hipSuccess) return MSIM_E_HIP;
     if (class_of && hipMemcpy(map.get(), class_of, m * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
         return MSIM_E_HIP;
     size_t at = 0;
@@ -439,6 +498,7 @@ int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, i
         const uint64_t cn = runs - off < chunk ? runs - off : chunk;
         Resident &k = kept[at];
         k.runs = cn;
+        k.begin = run_begin + off;
         if (!k.rec.alloc(cn * np * mc * sizeof(msim_run_record)) || !k.bh.alloc(cn * np * sizeof(uint32_t)))
             return MSIM_E_HIP;
         void *into = class_of ? rec.get() : k.rec.get();
@@ -446,6 +506,10 @@ int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, i
         if (rc) return rc;
         if (class_of) {
             rc = msim_fold_launch(m, np, cn, rec.get(), map.get(), mc, k.rec.get(), s);
+            if (rc) return rc;
+        }
+        if (boot) {
+            rc = msim_boot_weights_launch(boot->seed, run_begin + off, cn, boot->replicates, bootW.get(), s);
             if (rc) return rc;
         }
         if (tail) {
@@ -497,6 +561,10 @@ int run_order_impl(uint32_t m, uint32_t np, uint64_t run_begin, uint64_t runs, i
         }
         memcpy(tail->out_moments, acc_m.data(), n_mom * sizeof(uint64_t));
         memcpy(tail->out_tails, acc_t.data(), n_tw * sizeof(uint64_t));
+    }
+    if (boot) {
+        rc = run_boot_job(*boot, mc, np, kept, bootW, s);
+        if (rc) return rc;
     }
     if (opt_sums) memcpy(opt_sums, acc_s.data(), n_sums * sizeof(uint64_t));
     msim_sums_to_stats((const msim_sums *)acc_s.data(), np * m, out_stats);
@@ -572,6 +640,44 @@ int msim_sweep_run_tails(const msim_sweep *sweep, uint64_t run_begin, uint64_t r
             return msim_sweep_launch(sweep, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
         },
         &job);
+}
+
+int msim_run_bootstrap(const msim_config *cfg, uint64_t run_begin, uint64_t n_runs, uint32_t seed_base, int device,
+                       const uint32_t *class_of_or_NULL, uint32_t n_classes, const uint64_t *ranks, uint32_t n_ranks,
+                       const msim_boot_item *items, uint32_t n_items, const double *qs, uint32_t n_q,
+                       uint32_t replicates, uint64_t boot_seed, msim_stats *out_stats, msim_sums *opt_sums,
+                       msim_order_stat *out_order, uint64_t *out_W, msim_boot_row *out_rows)
+{
+    if (!cfg) return MSIM_E_INVALID;
+    msim_pipeline_layout pl;
+    const bool general = msim_pipeline_info(cfg, 1, &pl) == MSIM_OK && pl.uses_pipeline == 4;
+    const BootJob job = {items, n_items, qs, n_q, replicates, boot_seed, out_W, out_rows};
+    return run_order_impl(
+        msim_config_miner_count(cfg), 1, run_begin, n_runs, device, class_of_or_NULL, n_classes, ranks, n_ranks,
+        out_stats, opt_sums, out_order, general, [&](uint64_t n) { return msim_workspace_bytes(cfg, n); },
+        [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
+            return msim_launch(cfg, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
+        },
+        nullptr, &job);
+}
+
+int msim_sweep_run_bootstrap(const msim_sweep *sweep, uint64_t run_begin, uint64_t runs_per_point, uint32_t seed_base,
+                             int device, const uint32_t *class_of_or_NULL, uint32_t n_classes, const uint64_t *ranks,
+                             uint32_t n_ranks, const msim_boot_item *items, uint32_t n_items, const double *qs,
+                             uint32_t n_q, uint32_t replicates, uint64_t boot_seed, msim_stats *out_stats,
+                             msim_sums *opt_sums, msim_order_stat *out_order, uint64_t *out_W,
+                             msim_boot_row *out_rows)
+{
+    if (!sweep) return MSIM_E_INVALID;
+    const BootJob job = {items, n_items, qs, n_q, replicates, boot_seed, out_W, out_rows};
+    return run_order_impl(
+        msim_sweep_miner_count(sweep), msim_sweep_point_count(sweep), run_begin, runs_per_point, device,
+        class_of_or_NULL, n_classes, ranks, n_ranks, out_stats, opt_sums, out_order, false,
+        [&](uint64_t n) { return msim_sweep_workspace_bytes(sweep, n); },
+        [&](uint64_t b, uint64_t n, void *sums, void *rec, void *bh, void *status, void *ws, size_t wsb, hipStream_t s) {
+            return msim_sweep_launch(sweep, b, n, seed_base, sums, rec, bh, status, ws, wsb, s);
+        },
+        nullptr, &job);
 }
 
 }  // extern "C"

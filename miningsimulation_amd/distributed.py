@@ -458,3 +458,105 @@ def run_sharded_tails(sim, n_total: int, seed_base: int, q=0.05, ranks=None, spe
         n_runs=n_total,
     )
     return make_result([res], sel, qs, order, n_total, specs, host[6 * m + 2:].numpy(), tails.cpu().numpy())
+
+
+def run_sharded_bootstrap(sim, n_total: int, seed_base: int, items=None, qs=(0.05,), replicates: int = 200,
+                          boot_seed: Optional[int] = None, run_begin: int = 0, stream=None,
+                          launch: Optional[Callable] = None, launch_boot_weights: Optional[Callable] = None,
+                          launch_boot_begin: Optional[Callable] = None, launch_boot_count: Optional[Callable] = None,
+                          launch_boot_step: Optional[Callable] = None, launch_boot_below: Optional[Callable] = None,
+                          device=None, max_chunk: int = MAX_LAUNCH_RUNS):
+    """run_sharded plus the Poisson bootstrap of `items` (bootstrap.py) over ALL n_total runs: this rank's shard runs
+    through msim_launch in chunks whose records stay resident, and every chunk adds its weights to W with
+    msim_boot_weights_launch. W rides behind the sums and status words in the FIRST all-reduce; every rank then
+    computes the same ranks from the complete W and begins the same workspace. Per pass msim_boot_count_launch runs on
+    every resident buffer, ONE all-reduce of the workspace's counts view follows, and msim_boot_step_launch; after
+    the last step msim_boot_below_launch runs on every buffer and ONE all-reduce adds the rows' s_hi and s_lo: ten
+    all-reduces per job. A weight depends on the absolute run index alone and everything reduced is an integer sum
+    over runs, so the result is identical on every rank and for every world size.
+
+    Returns a BootstrapResult whose `order` is empty (replicate 0 of an item is its order statistic over all runs).
+    The `launch*` callables replace sim.launch, bootstrap.launch_boot_weights and sim.launch_boot_* (same
+    signatures, workspace None for the launch) so that CPU ranks with a gloo group can exercise the job."""
+    import contextlib
+
+    import torch
+    import torch.distributed as dist
+
+    from . import bootstrap as bs
+    from ._lib import MsimSums
+    from .quantiles import RANK_PASSES, quantile_rank
+    from .simulation import SimulationResult, sums_to_stats
+
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    begin, n = shard(n_total, world, rank)
+    m = len(sim.miners)
+    B = int(replicates)
+    qs = bs._check_call(n_total, qs, B)
+    seed = bs.DEFAULT_BOOT_SEED if boot_seed is None else int(boot_seed) & (2 ** 64 - 1)
+    items, _ = bs.items_struct(bs.own_bootstrap(1, m) if items is None else items, 1, m, len(qs))
+    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    ws_words = bs.boot_workspace_bytes(len(items), B) // 8
+    c_off, c_words = bs.boot_counts_view(len(items), B)
+    assert c_off % 8 == 0 and c_off // 8 + c_words == ws_words  # the counts end the workspace
+    # the sums, the two status words and W in one buffer: the first all-reduce
+    head = torch.zeros(6 * m + 2 + B, dtype=torch.int64, device=dev)
+    sums, status, d_W = head[:6 * m].view(m, 6), head[6 * m:6 * m + 2], head[6 * m + 2:]
+    part = torch.zeros((m, 6), dtype=torch.int64, device=dev)
+    pst = torch.zeros(2, dtype=torch.int32, device=dev)
+    d_ws = torch.zeros(ws_words, dtype=torch.int64, device=dev)
+    rows = torch.zeros((len(items), B, bs.ROW_WORDS), dtype=torch.int64, device=dev)
+    rst = torch.zeros(1, dtype=torch.int32, device=dev)
+    chunk = min(n, max_chunk)
+    ws = None
+    if n and launch is None:
+        ws = torch.empty(sim.workspace_bytes(chunk), dtype=torch.uint8, device=dev)
+    kept = []
+    ctx = torch.cuda.stream(stream) if (stream is not None and dev.type == "cuda") else contextlib.nullcontext()
+    if stream is not None and dev.type == "cuda":
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    with ctx:
+        for off in range(0, n, max(chunk, 1)):
+            cn = min(chunk, n - off)
+            first = run_begin + begin + off
+            rec = torch.zeros((cn, m, 2), dtype=torch.int32, device=dev)
+            bh = torch.zeros(cn, dtype=torch.int32, device=dev)
+            (launch or sim.launch)(cn, first, seed_base, part, ws, pst, d_per_run=rec, d_best_height=bh, stream=stream)
+            (launch_boot_weights or bs.launch_boot_weights)(seed, first, cn, B, d_W, stream=stream)
+            sums += part
+            status += pst
+            kept.append((cn, first, rec, bh))
+        if world > 1:
+            dist.all_reduce(head)
+        W = [int(w) & (2 ** 64 - 1) for w in d_W.cpu().tolist()]  # complete, and the same on every rank
+        (launch_boot_begin or sim.launch_boot_begin)(items, B, bs.boot_ranks(W, qs), len(qs), d_ws, stream=stream)
+        for p in range(RANK_PASSES):
+            for cn, first, rec, bh in kept:
+                (launch_boot_count or sim.launch_boot_count)(cn, rec, bh, seed, first, len(items), B, p, d_ws, stream=stream)
+            if world > 1:
+                dist.all_reduce(d_ws[c_off // 8:])
+            (launch_boot_step or sim.launch_boot_step)(len(items), B, p, d_ws, rows, rst, stream=stream)
+        # every rank holds the same rows {value, below, equal, 0, 0}; the below words are sums over its own runs
+        for cn, first, rec, bh in kept:
+            (launch_boot_below or sim.launch_boot_below)(cn, rec, bh, seed, first, len(items), B, d_ws, rows, stream=stream)
+        if world > 1:
+            below = rows[:, :, 3:].contiguous()
+            dist.all_reduce(below)
+            rows[:, :, 3:] = below
+    if stream is not None and dev.type == "cuda":
+        torch.cuda.current_stream(dev).wait_stream(stream)
+    host = head.cpu()
+    if int(host[6 * m + 1]) != 0:
+        raise RuntimeError(f"{int(host[6 * m + 1])} runs exceeded the compact state capacity")
+    if int(rst.cpu()[0]) != 0:
+        raise RuntimeError("a replicate's rank was not below its weight")
+    srows = host[:6 * m].view(m, 6).tolist()
+    u64 = (lambda v: int(v) & 0xFFFFFFFFFFFFFFFF)
+    res = SimulationResult(
+        stats_total=sums_to_stats([[u64(x) for x in r] for r in srows]),
+        sums=[MsimSums(r[0], r[1], u64(r[2]), u64(r[3]), u64(r[4]), u64(r[5])) for r in srows],
+        n_runs=n_total,
+    )
+    return bs.make_result([res], [quantile_rank(n_total, q) for q in qs], qs, [], n_total, items, B, seed, W,
+                          rows.cpu().numpy())

@@ -28,6 +28,8 @@ from .moments import MOMENT_WORDS, HistSpec, moments_from_words
 from .quantiles import (QuantileResult, _launch_rank_begin, _launch_rank_count, _launch_rank_step, _run_quantiles,
                         rank_counts_view, rank_workspace_bytes)
 from .tails import TailResult, TailSpec, _launch_tails, _run_tails
+from .bootstrap import (DEFAULT_BOOT_SEED, BootItem, BootstrapResult, _launch_boot_begin, _launch_boot_below,
+                        _launch_boot_count, _launch_boot_step, _run_bootstrap)
 
 SIM_DURATION_MS = 31_556_952_000  # main.cpp:7 std::chrono::months{12}
 SIM_RUNS = 16 * 2048              # main.cpp:10
@@ -401,6 +403,41 @@ class Simulation:
         (tails.items_words) and d_tails int64 [n_items, 42] (overwritten); the other buffers as launch_moments."""
         _launch_tails(columns or len(self.miners), 1, n_runs, d_per_run, d_best_height, d_items, n_items, d_tails, stream)
 
+    def run_bootstrap(self, n_runs: int, items: Optional[Sequence[BootItem]] = None, qs: Sequence[float] = (0.05,),
+                      replicates: int = 200, boot_seed: int = DEFAULT_BOOT_SEED,
+                      class_of: Optional[Sequence[int]] = None, n_classes: Optional[int] = None,
+                      seed_base: int = DEFAULT_SEED_BASE, run_begin: int = 0, device: int = 0) -> BootstrapResult:
+        """msim_run_bootstrap: run_quantiles() at `qs` plus the Poisson bootstrap of `items` (bootstrap.own_bootstrap
+        by default: every column's share at qs[0]) with `replicates` replicates, replicate 0 being the data.
+        result.se(i), result.shortfall_se(i), result.interval(i), result.difference(i, j) and
+        report_bootstrap(miners, result) work on it."""
+        return _run_bootstrap(lib.msim_run_bootstrap, "msim_run_bootstrap", self._h, 1, len(self.miners), n_runs, items,
+                              qs, replicates, boot_seed, class_of, n_classes, run_begin, seed_base, device)
+
+    def launch_boot_begin(self, items: Sequence[BootItem], replicates: int, ranks: Sequence[int], n_q: int, d_ws,
+                          stream=None, columns: Optional[int] = None) -> None:
+        """msim_boot_begin_launch on the current device: ranks is [n_q][replicates] flat (bootstrap.boot_ranks of the
+        complete W), d_ws a buffer of bootstrap.boot_workspace_bytes(len(items), replicates) bytes."""
+        _launch_boot_begin(columns or len(self.miners), 1, items, replicates, ranks, n_q, d_ws, stream)
+
+    def launch_boot_count(self, n_runs: int, d_per_run, d_best_height, boot_seed: int, run_begin: int, n_items: int,
+                          replicates: int, pass_: int, d_ws, stream=None, columns: Optional[int] = None) -> None:
+        """msim_boot_count_launch: pass `pass_` over a launch's records, whose first run is the absolute run
+        `run_begin`; adds to the workspace's counts."""
+        _launch_boot_count(columns or len(self.miners), 1, boot_seed, run_begin, n_runs, d_per_run, d_best_height,
+                           n_items, replicates, pass_, d_ws, stream)
+
+    def launch_boot_step(self, n_items: int, replicates: int, pass_: int, d_ws, d_rows, d_status, stream=None) -> None:
+        """msim_boot_step_launch; d_rows int64 [n_items, replicates, 5] (required at the last pass), d_status int32
+        [1] (added to)."""
+        _launch_boot_step(n_items, replicates, pass_, d_ws, d_rows, d_status, stream)
+
+    def launch_boot_below(self, n_runs: int, d_per_run, d_best_height, boot_seed: int, run_begin: int, n_items: int,
+                          replicates: int, d_ws, d_rows, stream=None, columns: Optional[int] = None) -> None:
+        """msim_boot_below_launch: adds the weighted halves of the keys below each row's value to d_rows."""
+        _launch_boot_below(columns or len(self.miners), 1, boot_seed, run_begin, n_runs, d_per_run, d_best_height,
+                           n_items, replicates, d_ws, d_rows, stream)
+
     def run_multi(self, n_runs: int, run_begin: int = 0, seed_base: int = DEFAULT_SEED_BASE,
                   devices: Sequence[int] = (0,)) -> SimulationResult:
         """msim_run_multi: the runs sharded over `devices` (one host thread each) and combined with one RCCL
@@ -636,6 +673,41 @@ class Sweep:
         """msim_tail_launch over a sweep launch's records."""
         _launch_tails(columns or self.m, len(self.sims), runs_per_point, d_per_run, d_best_height, d_items, n_items,
                       d_tails, stream)
+
+    def run_bootstrap(self, runs_per_point: int, items: Optional[Sequence[BootItem]] = None, qs: Sequence[float] = (0.05,),
+                      replicates: int = 200, boot_seed: int = DEFAULT_BOOT_SEED,
+                      class_of: Optional[Sequence[int]] = None, n_classes: Optional[int] = None,
+                      seed_base: int = DEFAULT_SEED_BASE, run_begin: int = 0, device: int = 0) -> BootstrapResult:
+        """msim_sweep_run_bootstrap: run_quantiles() at `qs` plus the Poisson bootstrap of `items` (bootstrap.own_bootstrap
+        by default: every column's share at qs[0]) with `replicates` replicates, replicate 0 being the data.
+        result.se(i), result.shortfall_se(i), result.interval(i), result.difference(i, j) and
+        report_bootstrap(miners, result) work on it."""
+        return _run_bootstrap(lib.msim_sweep_run_bootstrap, "msim_sweep_run_bootstrap", self._h, len(self.sims), self.m, runs_per_point, items,
+                              qs, replicates, boot_seed, class_of, n_classes, run_begin, seed_base, device)
+
+    def launch_boot_begin(self, items: Sequence[BootItem], replicates: int, ranks: Sequence[int], n_q: int, d_ws,
+                          stream=None, columns: Optional[int] = None) -> None:
+        """msim_boot_begin_launch on the current device: ranks is [n_q][replicates] flat (bootstrap.boot_ranks of the
+        complete W), d_ws a buffer of bootstrap.boot_workspace_bytes(len(items), replicates) bytes."""
+        _launch_boot_begin(columns or self.m, len(self.sims), items, replicates, ranks, n_q, d_ws, stream)
+
+    def launch_boot_count(self, runs_per_point: int, d_per_run, d_best_height, boot_seed: int, run_begin: int, n_items: int,
+                          replicates: int, pass_: int, d_ws, stream=None, columns: Optional[int] = None) -> None:
+        """msim_boot_count_launch: pass `pass_` over a launch's records, whose first run is the absolute run
+        `run_begin`; adds to the workspace's counts."""
+        _launch_boot_count(columns or self.m, len(self.sims), boot_seed, run_begin, runs_per_point, d_per_run, d_best_height,
+                           n_items, replicates, pass_, d_ws, stream)
+
+    def launch_boot_step(self, n_items: int, replicates: int, pass_: int, d_ws, d_rows, d_status, stream=None) -> None:
+        """msim_boot_step_launch; d_rows int64 [n_items, replicates, 5] (required at the last pass), d_status int32
+        [1] (added to)."""
+        _launch_boot_step(n_items, replicates, pass_, d_ws, d_rows, d_status, stream)
+
+    def launch_boot_below(self, runs_per_point: int, d_per_run, d_best_height, boot_seed: int, run_begin: int, n_items: int,
+                          replicates: int, d_ws, d_rows, stream=None, columns: Optional[int] = None) -> None:
+        """msim_boot_below_launch: adds the weighted halves of the keys below each row's value to d_rows."""
+        _launch_boot_below(columns or self.m, len(self.sims), boot_seed, run_begin, runs_per_point, d_per_run, d_best_height,
+                           n_items, replicates, d_ws, d_rows, stream)
 
     def workspace_bytes(self, runs_per_point: int) -> int:
         return int(lib.msim_sweep_workspace_bytes(self._h, runs_per_point))
