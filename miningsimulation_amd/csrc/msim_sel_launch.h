@@ -10,8 +10,13 @@
 //   G  msim_gen_kernel          the runs E2 could not finish (a chain outgrew the 16-height window: a
 //                               selfish majority), on the general engine's explicit chains (msim_general.h).
 //   F  msim_sel_finalize        one workgroup per (point, summed value).
+//
+// Everything but the launch functions is plain data and compiles without HIP: the test-only host build of the
+// engine (tests/native/sel_host.cpp) takes the device's capacities from here.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 
 #include "msim_dispatch.h"
 #include "msim_fastdraw.h"
@@ -83,6 +88,7 @@ struct SegArgs {
 };
 constexpr uint32_t SEG_OVERFLOW = 0xFFFFFFFFu;
 
+#if defined(__HIPCC__)
 // E1 / E2 for miner count m and selfish class (1, 2, 4); SW / ST for miner count m; dispatch in msim_common.hip.
 hipError_t launch_sel(const SelArgs &a, uint32_t m, uint32_t ns_class, hipStream_t s);
 hipError_t launch_sel_retry(const SelArgs &a, uint32_t m, uint32_t ns_class, hipStream_t s);
@@ -105,6 +111,7 @@ MSIM_FOR_EACH_M(MSIM_DECL_SEL)
 hipError_t launch_sel_finalize(const uint64_t *partials, uint32_t n_points, uint32_t wpp, uint32_t nvals,
                                const uint64_t *retry_sums, uint64_t *out, const uint32_t *counts, uint32_t *status,
                                hipStream_t s);
+#endif  // __HIPCC__
 
 inline uint32_t sel_ns_class(uint32_t ns) { return ns <= 1 ? 1u : (ns == 2 ? 2u : 4u); }
 

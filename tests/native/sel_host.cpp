@@ -1,11 +1,24 @@
 // sel_host.cpp — TEST INFRASTRUCTURE: a host (CPU) build of the product's entity engine
 // (miningsimulation_amd/csrc/msim_sel.h) so its algorithm can be checked against the oracle on machines
 // without a GPU. Never part of the product path (libmsim.so is GPU-only).
+//
+// Capacity classes (the `caps` argument of sel_run, see run_caps). The device's own classes take their cold-slot
+// count from msim_sel_launch.h (SEL_NC), the hot capacities are those msim_sel_kernels.hip instantiates:
+//   E1, one selfish miner, the mixed schedule              <1, 4, 1, SEL_NC>   caps 12
+//   E1, one selfish miner, the engine for every find       <1, 4, 1, SEL_NC>   caps 20 (MSIM_SEL_NO_MACRO, a 0 ms delay)
+//   E1, several selfish miners, the engine alone           <2, 4, 2, SEL_NC>   caps 0
+//   E2, mixed for one selfish miner and delays >= 1 ms     <4, 16, 4, SEL_NC>  caps 21
+//   E2, the engine alone whatever the network              <4, 16, 4, SEL_NC>  caps 22 (what E2 runs when E1 ran caps 20)
+//   E2 of a sweep whose largest selfish class is 4         <4, 16, 4, SEL_NC>  caps 23 (the engine alone, instantiated
+//                                                                               for four selfish miners, for every point)
+// Class 1 (<4, 16, 4, 6>, "retry capacities") has six cold slots: it is wider than anything the device runs and is
+// NOT the device's E2; it stays for the tests that want every run finished.
 #include <stdint.h>
 #include <string.h>
 
 #include "../../miningsimulation_amd/csrc/msim_dispatch.h"
 #include "../../miningsimulation_amd/csrc/msim_sel.h"
+#include "../../miningsimulation_amd/csrc/msim_sel_launch.h"
 #include "../../miningsimulation_amd/csrc/msim_selm.h"
 
 using namespace msim;
@@ -139,20 +152,30 @@ template <int M, int NS>
 void run_caps(int caps, const int64_t *prop, const uint32_t *sids, HostSrc &src, int64_t D, SelOut &o)
 {
     // 0: the device E1 capacities (msim_sel_launch.h), 3: a wider register class, 1: retry capacities,
-    // 2: one hot slot of everything (the cold paths run constantly), 4: no cold slots (error paths)
+    // 2: one hot slot of everything (the cold paths run constantly), 4: no cold slots (error paths);
+    // 20 - 23: the device's E1 engine-alone and E2 classes (the file's head)
+    if (caps >= 20) {
+        bool ok = NS == 1 && caps == 21;
+        for (int k = 0; k < M; ++k) ok = ok && prop[k] >= 1;
+        if (caps == 20 && NS == 1) run_one<M, NS, 1, 4, 1, SEL_NC>(prop, sids, src, D, o);
+        else if (caps == 20) run_one<M, NS, 2, 4, 2, SEL_NC>(prop, sids, src, D, o);
+        else if (ok) run_mixed<M, NS, 4, 16, 4, SEL_NC>(prop, sids, src, D, o);
+        else run_one<M, NS, 4, 16, 4, SEL_NC>(prop, sids, src, D, o);
+        return;
+    }
     if (caps >= 10 && NS == 1) {  // the mixed schedule (settled form + engine), engine capacities caps - 10
         bool ok = true;
         for (int k = 0; k < M; ++k) ok = ok && prop[k] >= 1;
         if (ok) {
-            if (caps == 10) run_mixed<M, NS, 2, 4, 2, 4>(prop, sids, src, D, o);
-            else if (caps == 11) run_mixed<M, NS, 1, 2, 1, 4>(prop, sids, src, D, o);
-            else run_mixed<M, NS, 1, 4, 1, 4>(prop, sids, src, D, o);
+            if (caps == 10) run_mixed<M, NS, 2, 4, 2, SEL_NC>(prop, sids, src, D, o);
+            else if (caps == 11) run_mixed<M, NS, 1, 2, 1, SEL_NC>(prop, sids, src, D, o);
+            else run_mixed<M, NS, 1, 4, 1, SEL_NC>(prop, sids, src, D, o);
             return;
         }
         caps -= 10;
     }
     if (caps >= 10) caps -= 10;
-    if (caps == 0) run_one<M, NS, 2, 4, 2, 4>(prop, sids, src, D, o);
+    if (caps == 0) run_one<M, NS, 2, 4, 2, SEL_NC>(prop, sids, src, D, o);
     else if (caps == 1) run_one<M, NS, 4, 16, 4, 6>(prop, sids, src, D, o);
     else if (caps == 2) run_one<M, NS, 1, 4, 1, 6>(prop, sids, src, D, o);
     else if (caps == 3) run_one<M, NS, 3, 8, 3, 4>(prop, sids, src, D, o);
@@ -205,7 +228,8 @@ extern "C" int sel_run(const uint64_t *weights, const int64_t *prop, const uint8
     memset(&o, 0, sizeof(o));
 #define CASE(MM)                                                                                 \
     case MM:                                                                                       \
-        if (ns == 0) run_caps<MM, 0>(caps, prop, sids, src, duration_ms, o);                      \
+        if (caps == 23) run_caps<MM, 4>(caps, prop, sids, src, duration_ms, o);                   \
+        else if (ns == 0) run_caps<MM, 0>(caps, prop, sids, src, duration_ms, o);                 \
         else if (ns == 1) run_caps<MM, 1>(caps, prop, sids, src, duration_ms, o);                 \
         else if (ns == 2) run_caps<MM, 2>(caps, prop, sids, src, duration_ms, o);                 \
         else run_caps<MM, 4>(caps, prop, sids, src, duration_ms, o);                              \

@@ -294,3 +294,95 @@ def test_mixed_equals_engine_alone(sel):
         b = sel(percs, props, selfish, D // 52, 5000 + 2 * r, 5001 + 2 * r, 10)
         assert a[0] == 0 and b[0] == 0
         assert np.array_equal(a[1], b[1]) and a[2] == b[2]
+
+
+# ---------------------------------------------------------------- the device's own capacity classes
+# caps 12 / 20 / 0 are E1's classes and 21 / 22 / 23 E2's (tests/native/sel_host.cpp); class 1 above has six cold
+# slots and is wider than the device's E2. tests/sel_flag_cases.py holds networks that exceed these classes and the
+# prediction tests/test_gpu_selfish_flags.py holds the device's counters to.
+import sel_flag_cases as fc
+
+
+@pytest.fixture(scope="module")
+def flag_run(native_tests):
+    return fc.load(native_tests["sel_host"])
+
+
+@pytest.mark.parametrize("h,prop", [(40, 1000), (49, 30_000), (45, 10_000), (25, 100), (10, 30_000), (49, 100),
+                                    (30, 5000)])
+def test_selfish_full_year_device_e2(sel, oracle, h, prop):
+    """test_selfish_full_year's corners at the device's classes: what E1's class cannot hold is flagged, and E2's real
+    class (four cold slots, mixed schedule) is exact or flags in turn; the engine-alone E2 likewise."""
+    percs = [h, 59 - h, 12, 11, 8, 5, 3, 1, 1]
+    for r in range(2):
+        si, sp = 1000 + 2 * r, 1001 + 2 * r
+        for e1, e2 in ((fc.E1_MIXED, fc.E2_DEVICE), (fc.E1_ENGINE_ONE, fc.E2_ENGINE)):
+            if _check(sel, oracle, percs, [prop] * 9, [True] + [False] * 8, D, si, sp, caps=e1, allow_err=True):
+                _check(sel, oracle, percs, [prop] * 9, [True] + [False] * 8, D, si, sp, caps=e2, allow_err=True)
+        _check(sel, oracle, percs, [prop] * 9, [True] + [False] * 8, D, si, sp, caps=fc.E2_DEVICE)
+
+
+def _exact_or_flagged(flag_run, oracle, case, p, n, classes):
+    """Every run a class finishes equals the oracle; returns the flag vectors per class."""
+    f, s, _, _ = fc.oracle_runs(oracle, case, n)
+    out = []
+    for caps in classes:
+        errs = np.zeros(n, dtype=np.int64)
+        for r in range(n):
+            errs[r], rec, bh = flag_run(case, r, caps)
+            if not errs[r]:
+                assert np.array_equal(rec[:, 0], f[r]) and np.array_equal(rec[:, 1], s[r]), (case.name, caps, r)
+                assert bh == int(f[r].sum()), (case.name, caps, r)
+        out.append(errs)
+    return out
+
+
+@pytest.mark.parametrize("name", list(fc.CASES))
+def test_flag_case(flag_run, oracle, name):
+    """One row of the case table: at E1's and E2's device class every unflagged run equals the oracle, the prediction
+    is those very error words, and the row's preconditions hold on it (flag counts in tests/sel_flag_cases.py's terms;
+    DESIGN §5 lists them)."""
+    case = fc.CASES[name]
+    p = fc.predict(flag_run, case)
+    e1, e2 = _exact_or_flagged(flag_run, oracle, case, p, fc.RUNS, (fc.e1_class(case), fc.e2_class(case)))
+    assert np.array_equal(e1, p.e1)
+    # a run E1 flags is flagged or exact at E2 (exactness checked above); E2 flags nothing E1 finished
+    assert np.array_equal(np.where(p.e1 != 0, e2, 0), p.e2)
+    assert not (e2[p.e1 == 0]).any(), name
+    fc.check_preconditions(case, p)
+    f, s, _, _ = fc.oracle_runs(oracle, case)
+    done = p.e2 == 0
+    assert np.array_equal(p.rec[done, :, 0], f[done]) and np.array_equal(p.rec[done, :, 1], s[done])
+    assert np.array_equal(p.bh[done], f[done].sum(axis=1))
+
+
+@pytest.mark.parametrize("name", ["c3_900", "c3_1800"])
+def test_flag_case_engine_alone(flag_run, oracle, name):
+    """The same networks with the engine for every find (MSIM_SEL_NO_MACRO): classes <1, 4, 1> and E2's engine alone."""
+    case = fc.CASES[name]
+    p = fc.predict(flag_run, case, no_macro=True)
+    e1, e2 = _exact_or_flagged(flag_run, oracle, case, p, fc.RUNS, (fc.E1_ENGINE_ONE, fc.E2_ENGINE))
+    assert np.array_equal(e1, p.e1) and np.array_equal(np.where(p.e1 != 0, e2, 0), p.e2)
+    fc.check_preconditions(case, p)
+
+
+@pytest.mark.parametrize("name", ["c3_1", "c3_1800", "c3_three"])
+def test_flag_case_sweep_class(flag_run, oracle, name):
+    """E2 of a sweep runs every point at the largest selfish class of the sweep, the engine alone: with unused
+    selfish entities a network keeps its results and its flags."""
+    case = fc.CASES[name]
+    own, ns4 = _exact_or_flagged(flag_run, oracle, case, None, 100, (fc.E2_ENGINE, fc.E2_ENGINE_NS4))
+    assert np.array_equal(own, ns4), name
+
+
+@pytest.mark.parametrize("every", [1, 2, 5, 17])
+def test_flag_cases_early_folds(flag_run, every):
+    """A capacity flag is a function of a run's event sequence: folding early (as the device does when any lane of the
+    wave is due) moves no ACT, GRP or QUE flag of these cases at either class."""
+    for name in ("c3_900", "c3_2400", "f15_900", "two_5400", "t15_1200", "c3_three"):
+        case = fc.CASES[name]
+        p = fc.predict(flag_run, case)
+        for r in range(0, fc.RUNS, 2):
+            assert flag_run(case, r, fc.e1_class(case), fold_every=every)[0] == p.e1[r], (name, r)
+            if p.e1[r]:
+                assert flag_run(case, r, fc.e2_class(case), fold_every=every)[0] == p.e2[r], (name, r)
